@@ -8,6 +8,10 @@ bucketed RCCL all-reduce overlap + fused SGD — bf16 compute, batch 128/GPU,
 synthetic CIFAR-shaped data, random-init weights (no network for datasets).
 
 Single GPU: python bench.py --gpus 1 --steps 30 --warmup 10
+A plain run sets up, warms up, times --steps steps and prints one JSON line;
+--dump-outputs DIR also writes what the last timed step computed as .npy files
+(same arguments -> same inputs, so two builds can be diffed output for output).
+--full is the switch for any extra measurement beyond the headline figure.
 Multi-GPU (launched by the driver): python -m torch.distributed.run --nnodes=1
   --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
@@ -17,6 +21,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -24,6 +29,23 @@ from cilfw import ops
 from cilfw.distributed import DataParallelEngine
 from cilfw.models import CilModel
 from cilfw.optim import FlatSGD
+
+
+PARAM_SAMPLE = 4 * 1024 * 1024  # elements of flat_params kept in a dump (16 MB)
+
+
+def dump_outputs(out_dir, last, flat_params):
+    """Write the last step's outputs as float32 .npy (well under 64 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in last.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy().astype(np.float32))
+    p = flat_params.detach().float().cpu().numpy()
+    if p.size > PARAM_SAMPLE:  # fixed, seeded sample of the updated weights
+        idx = np.sort(np.random.RandomState(0).choice(
+            p.size, PARAM_SAMPLE, replace=False))
+        p = p[idx]
+    np.save(os.path.join(out_dir, "params.npy"), p.astype(np.float32))
 
 
 def main():
@@ -40,6 +62,14 @@ def main():
     p.add_argument("--no_graph", dest="graph", action="store_false",
                    default=True,
                    help="disable hipGraph capture of the training step")
+    p.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                   default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's outputs "
+                        "(loss terms, logits, updated params) to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements that are not needed for the "
+                        "headline figure (none at present: a plain run is "
+                        "already the whole benchmark)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -84,6 +114,10 @@ def main():
     # captured as a forked hipGraph)
     tstream = torch.cuda.Stream() if (use_cuda and teacher is not None) else None
 
+    # what a caller of step() receives; under hipGraph these are the graph's
+    # static output tensors, refreshed by every replay
+    last = {}
+
     def step():
         opt.zero_grad()
         if tstream is not None:
@@ -103,6 +137,11 @@ def main():
         loss.backward()
         engine.finalize()
         opt.step()
+        last["loss"], last["loss_ce"], last["loss_kd"] = (
+            loss.detach(), _lce.detach(), _lkd.detach())
+        last["logits"] = logits.detach()
+        if teacher is not None:
+            last["teacher_logits"] = t_logits.detach()
 
     for _ in range(args.warmup):
         step()
@@ -152,6 +191,9 @@ def main():
         t = torch.tensor([elapsed], device=device if use_cuda else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, engine.flat_params)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1000.0
