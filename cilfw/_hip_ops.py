@@ -67,6 +67,7 @@ _PROTOS = {
     "cilfw_topk_correct": [c_vp] * 3 + [c_i] * 3 + [c_vp],
     "cilfw_herding_select": [c_vp] * 3 + [c_i] * 3 + [c_vp],
     "cilfw_herding_select_batch": [c_vp] * 6 + [c_i] * 3 + [c_vp],
+    "cilfw_crop_resize": [c_vp] * 7 + [c_i] * 7 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -631,6 +632,52 @@ def topk_correct(logits, targets, maxk):
                             _stream())
     _check("topk_correct")
     return counts
+
+
+_CROP_RESIZE_MODES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}
+
+
+def crop_resize(src, idx, params, flip, out_size, mean255, std255, dtype):
+    """Fused gather -> affine bilinear resample -> flip -> quantize ->
+    normalize (csrc/data.hip). src uint8 (M,Hs,Ws,C); idx int64 (N,) or None;
+    params fp32 (N,4) = (oy, ox, sy, sx); flip uint8 (N,). mean255/std255
+    None -> uint8 levels, else normalized ``dtype`` (fp32 / bf16)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.is_contiguous()
+    M, Hs, Ws, C = src.shape
+    S = int(out_size)
+    assert 1 <= C <= 4 and M >= 1 and Hs >= 1 and Ws >= 1 and S >= 1
+    assert S * S * C < 2 ** 31 and Hs * Ws * C < 2 ** 31
+    dev = src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and idx.dim() == 1 \
+            and idx.device == dev
+        idx = idx.contiguous()
+        N = idx.shape[0]
+    else:
+        N = M
+    assert params.shape == (N, 4) and params.dtype == torch.float32 \
+        and params.device == dev
+    assert flip.shape == (N,) and flip.dtype == torch.uint8 \
+        and flip.device == dev
+    params = params.contiguous()
+    flip = flip.contiguous()
+    if mean255 is None:
+        assert std255 is None
+        dtype = torch.uint8
+    else:
+        assert dtype in (torch.float32, torch.bfloat16), \
+            f"crop_resize: normalized output is fp32 or bf16 (got {dtype})"
+        mean255 = mean255.to(dev, torch.float32).reshape(-1).contiguous()
+        std255 = std255.to(dev, torch.float32).reshape(-1).contiguous()
+        assert mean255.numel() == C and std255.numel() == C
+    out = torch.empty(N, S, S, C, dtype=dtype, device=dev)
+    assert out.data_ptr() % 16 == 0  # the kernel stores 16-byte vectors
+    _lib.cilfw_crop_resize(_ptr(src), _ptr(idx), _ptr(params), _ptr(flip),
+                           _ptr(mean255), _ptr(std255), _ptr(out), c_i(M),
+                           c_i(N), c_i(Hs), c_i(Ws), c_i(C), c_i(S),
+                           c_i(_CROP_RESIZE_MODES[dtype]), _stream())
+    _check("crop_resize")
+    return out
 
 
 def herding_select(f, mu, m):

@@ -206,6 +206,83 @@ def translate_y(imgs, mag, sign):
     return _affine_sample(imgs, eye, offs)
 
 
+# ------------------------------------------- crop_resize parameter sampling
+#
+# ops.crop_resize maps output pixel (i, j) to source (oy + i*sy, ox + j*sx).
+# A crop box (y, x, h, w) resized to S is oy=y, ox=x, sy=(h-1)/(S-1),
+# sx=(w-1)/(S-1): the corner-to-corner map of scipy.ndimage.zoom(order=1)
+# that the host _resize uses.
+
+def _box_params(y, x, h, w, S):
+    d = float(max(S - 1, 1))
+    return torch.stack([y, x, (h - 1) / d, (w - 1) / d], dim=1).float()
+
+
+def rrc_params(N, Hs, Ws, S, generator, device, scale=(0.08, 1.0),
+               ratio=(3 / 4, 4 / 3)):
+    """RandomResizedCrop boxes + flips for N samples, the host rule
+    (transforms.random_resized_crop) vectorised: ten (area, aspect)
+    candidates per sample, first one that fits wins and gets a uniform
+    integer offset; none fitting -> center crop of side min(Hs, Ws). All on
+    ``device`` from ``generator``, no host sync. Returns (params fp32 (N,4),
+    flip uint8 (N,))."""
+    def rand(*shape):
+        return torch.rand(*shape, device=device, generator=generator)
+
+    area = Hs * Ws * (scale[0] + rand(N, 10) * (scale[1] - scale[0]))
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    ar = torch.exp(lo + rand(N, 10) * (hi - lo))
+    w = torch.sqrt(area * ar).round().clamp_min(1.0)
+    h = torch.sqrt(area / ar).round().clamp_min(1.0)
+    ok = (w <= Ws) & (h <= Hs)
+    first = ok.float().argmax(dim=1, keepdim=True)  # first fitting candidate
+    fits = ok.any(dim=1)
+    side = float(min(Hs, Ws))
+    w = torch.where(fits, w.gather(1, first).squeeze(1),
+                    torch.full((N,), side, device=device))
+    h = torch.where(fits, h.gather(1, first).squeeze(1),
+                    torch.full((N,), side, device=device))
+    # uniform integer offset in [0, Hs-h] (rand < 1, the min guards fp32
+    # rounding of the product up to the open end)
+    y = torch.minimum((rand(N) * (Hs - h + 1)).floor(), Hs - h)
+    x = torch.minimum((rand(N) * (Ws - w + 1)).floor(), Ws - w)
+    y = torch.where(fits, y, torch.full((N,), float((Hs - int(side)) // 2),
+                                        device=device))
+    x = torch.where(fits, x, torch.full((N,), float((Ws - int(side)) // 2),
+                                        device=device))
+    flip = (rand(N) < 0.5).to(torch.uint8)
+    return _box_params(y, x, h, w, S), flip
+
+
+def eval_params(N, Hs, Ws, S, device):
+    """EvalTransform for large inputs as one affine map: resize so the short
+    side becomes R = int(256/224*S) (the host resize is square, Z x Z), then
+    center-crop S. ``short == R`` skips the resize: scale exactly 1."""
+    R = int(256 / 224 * S)
+    short = min(Hs, Ws)
+    if short != R:
+        Z = max(int(round(Hs * (R / short))), R)
+        sy = (Hs - 1) / max(Z - 1, 1)
+        sx = (Ws - 1) / max(Z - 1, 1)
+        off = (Z - S) // 2
+        row = [off * sy, off * sx, sy, sx]
+    else:
+        row = [float((Hs - S) // 2), float((Ws - S) // 2), 1.0, 1.0]
+    params = torch.tensor(row, dtype=torch.float32, device=device)
+    return (params.view(1, 4).expand(N, 4).contiguous(),
+            torch.zeros(N, dtype=torch.uint8, device=device))
+
+
+def resize_params(N, Hs, Ws, S, device):
+    """Plain resize of the whole image to S x S (TrainTransform's ``no_aug``
+    branch); the identity when the stored size already is S."""
+    d = max(S - 1, 1)
+    params = torch.tensor([0.0, 0.0, (Hs - 1) / d, (Ws - 1) / d],
+                          dtype=torch.float32, device=device)
+    return (params.view(1, 4).expand(N, 4).contiguous(),
+            torch.zeros(N, dtype=torch.uint8, device=device))
+
+
 DEVICE_OPS = [autocontrast, equalize, invert, rotate, posterize, solarize,
               solarize_add, color, contrast, brightness, sharpness, shear_x,
               shear_y, translate_x, translate_y]

@@ -8,6 +8,13 @@ assembles every batch on-device: gather -> random crop(+pad) -> horizontal
 flip -> [RandAugment / color-jitter / random-erasing, see device_augment.py]
 -> normalize -> bf16, all torch index ops on the GPU.
 
+Large inputs (``--input_size > 64``) use the resampling crop modes instead
+(``crop_mode`` "rrc" / "eval" / "resize"): RandomResizedCrop + flip for
+training, resize + center-crop for evaluation, exactly the host transform
+contract, from sources of any stored size. Those are ONE fused HIP launch per
+batch (``ops.crop_resize``, csrc/data.hip): gather -> bilinear resample ->
+flip -> quantize -> normalize straight from the resident uint8 tensor.
+
 Sharding is the torch-DistributedSampler contract via the single shared
 implementation ``cilfw.data.sampler.compute_shard`` (same seed+epoch
 permutation on every rank, pad-by-repetition, rank-strided slice).
@@ -28,7 +35,8 @@ from .sampler import compute_shard
 class GpuTaskLoader:
     def __init__(self, taskset, batch_size, device, mean, std, world=1, rank=0,
                  shuffle=True, seed=0, augment=True, drop_last=True,
-                 dtype=torch.bfloat16, pad=4, extra=None, aug_pipeline=None):
+                 dtype=torch.bfloat16, pad=4, extra=None, aug_pipeline=None,
+                 crop_mode="pad", out_size=None):
         assert taskset.x.dtype == np.uint8, \
             "GpuTaskLoader needs array-backed images (not lazy paths)"
         images = torch.from_numpy(np.ascontiguousarray(taskset.x)).to(device)
@@ -52,6 +60,16 @@ class GpuTaskLoader:
         self.drop_last = drop_last
         self.dtype = dtype
         self.pad = pad
+        # crop_mode: "pad" = zero-pad + random crop at the stored size (small
+        # inputs, the default); "rrc" = RandomResizedCrop + flip; "eval" =
+        # resize + center-crop; "resize" = plain resize. The last three go
+        # through ops.crop_resize and produce out_size x out_size batches
+        # from sources of any stored size.
+        assert crop_mode in ("pad", "rrc", "eval", "resize"), crop_mode
+        self.crop_mode = crop_mode
+        self.out_size = int(out_size if out_size is not None
+                            else images.shape[1])
+        self._param_cache = {}
         self.epoch = 0
         self.mean = (torch.tensor(mean, device=device).view(1, 1, 1, -1)
                      * 255.0)
@@ -78,37 +96,73 @@ class GpuTaskLoader:
                               self.drop_last)
         return shard.to(self.device)
 
+    def _resample_params(self, n, g):
+        """(params, flip) rows for ops.crop_resize, per crop mode."""
+        from .device_augment import eval_params, resize_params, rrc_params
+        Hs, Ws = self.images.shape[1], self.images.shape[2]
+        mode = self.crop_mode
+        if mode == "rrc" and not self.augment:
+            mode = "eval"
+        if mode == "rrc":
+            return rrc_params(n, Hs, Ws, self.out_size, g, self.device)
+        key = (mode, n)  # eval / resize rows are constants: build once
+        if key not in self._param_cache:
+            fn = eval_params if mode == "eval" else resize_params
+            self._param_cache[key] = fn(n, Hs, Ws, self.out_size,
+                                        self.device)
+        return self._param_cache[key]
+
     def __iter__(self):
         shard = self._shard_indices()
         g = torch.Generator(device=self.device)
         g.manual_seed(self.seed * 1000003 + self.epoch * 131 + self.rank)
         nb = len(self)
         aug = self.aug_pipeline if self.augment else None
+        resample = self.crop_mode != "pad"
+        if resample:
+            from ..ops import crop_resize
         aug_imgs = None
         if aug is not None and (aug.enabled or aug.color_jitter > 0):
             # EPOCH-level batched RandAugment + jitter over the whole shard:
             # per-batch application is host-sync/launch-bound (~200 launches
             # + op-subset syncs per 128-batch cost 2/3 of step throughput);
             # one pass per epoch amortizes that ~40x. Results are integral
-            # 0..255 so they round-trip through uint8 exactly. (Order
-            # deviation vs the host pipeline: RA/jitter run before the
-            # per-batch pad-crop/flip instead of after — documented.)
-            srcs = self.images[shard]
+            # 0..255 so they round-trip through uint8 exactly.
+            # Order: the resampling modes (crop_mode rrc/eval/resize, large
+            # inputs) crop+flip FIRST, in uint8, then RA/jitter run on the
+            # crops - the host order crop -> flip -> RA -> jitter ->
+            # normalize -> erase. The small-input crop_mode="pad" path keeps
+            # its documented deviation: RA/jitter run before the per-batch
+            # pad-crop/flip instead of after.
             outs = []
-            for c0 in range(0, srcs.shape[0], 4096):
-                outs.append(aug(srcs[c0:c0 + 4096], g).to(torch.uint8))
+            for c0 in range(0, shard.shape[0], 4096):
+                if resample:
+                    sel = shard[c0:c0 + 4096]
+                    params, flip = self._resample_params(sel.shape[0], g)
+                    chunk = crop_resize(self.images, sel, params, flip,
+                                        self.out_size)
+                else:
+                    chunk = self.images[shard[c0:c0 + 4096]]
+                outs.append(aug(chunk, g).to(torch.uint8))
             aug_imgs = torch.cat(outs)
-            del outs, srcs
+            del outs
         for b in range(nb):
             idx = shard[b * self.batch_size:(b + 1) * self.batch_size]
-            if aug_imgs is not None:
-                imgs = aug_imgs[b * self.batch_size:
-                                (b + 1) * self.batch_size].float()
+            if resample and aug_imgs is None:
+                # one fused launch: resident uint8 -> normalized dtype
+                params, flip = self._resample_params(idx.shape[0], g)
+                imgs = crop_resize(self.images, idx, params, flip,
+                                   self.out_size, self.mean.view(-1),
+                                   self.std.view(-1), self.dtype)
             else:
-                imgs = self.images[idx].float()
-            if self.augment:
-                imgs = self._crop_flip(imgs, g)
-            imgs = ((imgs - self.mean) / self.std).to(self.dtype)
+                if aug_imgs is not None:
+                    imgs = aug_imgs[b * self.batch_size:
+                                    (b + 1) * self.batch_size].float()
+                else:
+                    imgs = self.images[idx].float()
+                if self.augment and not resample:
+                    imgs = self._crop_flip(imgs, g)
+                imgs = ((imgs - self.mean) / self.std).to(self.dtype)
             if aug is not None and aug.reprob > 0:
                 imgs = aug.erase(imgs, g)
             yield imgs, self.labels[idx], None

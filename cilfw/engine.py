@@ -43,6 +43,18 @@ def compute_dtype(args):
     return torch.float32
 
 
+def _crop_modes(args):
+    """(train, eval) GpuTaskLoader crop modes + out_size kwargs. Large inputs
+    (same threshold as TrainTransform.small) follow the host transform
+    contract: RandomResizedCrop for training (plain resize under --no_aug),
+    resize + center-crop for evaluation and feature extraction."""
+    if args.input_size <= 64:
+        return {}, {}
+    train = "resize" if args.no_aug else "rrc"
+    return (dict(crop_mode=train, out_size=args.input_size),
+            dict(crop_mode="eval", out_size=args.input_size))
+
+
 def _gpu_data_active(args, device, dataset):
     """--gpu_data engages for array-backed datasets on cuda devices; the env
     override CILFW_GPU_DATA_ON_CPU=1 lets tests exercise the same loader /
@@ -274,7 +286,7 @@ def extract_task_features(model, dataset, device, args):
         mean, std = DATASET_STATS[getattr(args, "_stats_key", "synthetic")]
         loader = GpuTaskLoader(dataset, args.batch_size, device, mean, std,
                                shuffle=False, augment=False, drop_last=False,
-                               dtype=dtype)
+                               dtype=dtype, **_crop_modes(args)[1])
     else:
         # un-augmented features on the CPU path too (the device path always
         # extracts with augment=False; advisor round-1 flagged the mismatch)
@@ -413,11 +425,13 @@ def _run_tasks(args, device, watchdog):
                 dataset_train, args.batch_size, device, mean, std,
                 world=world, rank=rank, shuffle=True, seed=args.seed,
                 augment=not args.no_aug, drop_last=True,
-                dtype=compute_dtype(args), extra=extra, aug_pipeline=aug)
+                dtype=compute_dtype(args), extra=extra, aug_pipeline=aug,
+                **_crop_modes(args)[0])
             val_loader = GpuTaskLoader(
                 dataset_val, args.batch_size, device, mean, std,
                 world=world, rank=rank, shuffle=False, augment=False,
-                drop_last=False, dtype=compute_dtype(args))
+                drop_last=False, dtype=compute_dtype(args),
+                **_crop_modes(args)[1])
         else:
             train_sampler = DistributedSampler(dataset_train, world, rank,
                                                shuffle=True, seed=args.seed)

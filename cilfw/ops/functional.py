@@ -777,3 +777,73 @@ def accuracy(logits, targets, topk=(1,)):
     correct = pred.eq(targets.view(-1, 1))
     n = targets.shape[0]
     return [correct[:, :k].any(dim=1).float().sum().item() * 100.0 / n for k in topk]
+
+
+# ------------------------------------------------- data: fused crop + resize
+
+
+def crop_resize_reference(src_u8, idx, params, flip, out_size, mean255=None,
+                          std255=None, dtype=None):
+    """Pure-torch statement of the crop_resize semantics (the HIP kernel's
+    oracle; also what CPU tensors run). Output pixel (i, j) of sample n:
+
+        jj = S-1-j if flip[n] else j
+        fy = oy + i*sy ; fx = ox + jj*sx            (params[n] = oy,ox,sy,sx)
+        y0 = clamp(floor(fy), 0, Hs-1) ; y1 = min(y0+1, Hs-1) ; ty = fy - y0
+        (same in x) ; bilinear in fp32 as a + t*(b - a), x first, then y
+        level = floor(clamp(v, 0, 255))
+
+    ``a + t*(b - a)`` is exact on constant regions (``a*(1-t) + b*t`` is not
+    and loses an LSB after the floor); the floor is the host pipeline's
+    numpy ``astype(uint8)`` after its resize."""
+    M, Hs, Ws, C = src_u8.shape
+    S = int(out_size)
+    dev = src_u8.device
+    if idx is None:
+        idx = torch.arange(M, device=dev)
+    N = idx.shape[0]
+    p = params.to(torch.float32)
+    oy, ox, sy, sx = (p[:, k:k + 1] for k in range(4))
+    ar = torch.arange(S, device=dev, dtype=torch.float32).view(1, S)
+    jj = torch.where(flip.view(N, 1) != 0, (S - 1) - ar, ar)
+    fy = oy + ar * sy
+    fx = ox + jj * sx
+    y0 = fy.floor().clamp(0, Hs - 1)
+    x0 = fx.floor().clamp(0, Ws - 1)
+    ty = (fy - y0).view(N, S, 1, 1)
+    tx = (fx - x0).view(N, 1, S, 1)
+    y0 = y0.long()
+    x0 = x0.long()
+    y1 = (y0 + 1).clamp(max=Hs - 1)
+    x1 = (x0 + 1).clamp(max=Ws - 1)
+    n_ix = idx.clamp(0, M - 1).view(N, 1, 1)
+
+    def tap(y, x):
+        return src_u8[n_ix, y.view(N, S, 1), x.view(N, 1, S)].float()
+
+    a, b = tap(y0, x0), tap(y0, x1)
+    top = a + tx * (b - a)
+    a, b = tap(y1, x0), tap(y1, x1)
+    bot = a + tx * (b - a)
+    v = (top + ty * (bot - top)).clamp_(0, 255).floor_()
+    if mean255 is None:
+        return v.to(torch.uint8)
+    out = (v - mean255.float().view(1, 1, 1, C)) \
+        / std255.float().view(1, 1, 1, C)
+    return out.to(dtype if dtype is not None else torch.float32)
+
+
+def crop_resize(src_u8, idx, params, flip, out_size, mean255=None,
+                std255=None, dtype=None):
+    """Gather rows ``idx`` of the resident uint8 NHWC tensor, resample each
+    through its affine map ``params`` (+ optional horizontal flip) to
+    ``out_size`` x ``out_size`` and either return uint8 levels (``mean255``
+    None) or the normalized ``dtype`` tensor. One HIP launch on a GPU; data
+    only, no autograd. See crop_resize_reference for the exact semantics."""
+    if use_hip(src_u8):
+        if mean255 is not None and dtype is None:
+            dtype = torch.float32
+        return ext().crop_resize(src_u8, idx, params, flip, out_size,
+                                 mean255, std255, dtype)
+    return crop_resize_reference(src_u8, idx, params, flip, out_size,
+                                 mean255, std255, dtype)
