@@ -81,10 +81,19 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_bwd_data_ksplit", 7),
                   ("cilfw_conv2d_bwd_data_can_fuse_bn", 8),
                   ("cilfw_conv2d_bwd_data_bn_gy", 3),
-                  ("cilfw_conv2d_bwd_weight_nslices", 7)]:
+                  ("cilfw_conv2d_bwd_weight_nslices", 7),
+                  ("cilfw_conv2d_fwd_route", 8),
+                  ("cilfw_conv2d_bwd_data_route", 9),
+                  ("cilfw_conv2d_bwd_weight_route", 8)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
+
+# route codes of csrc/conv.hip (enum order); the launchers branch on the same
+# C functions these queries call
+_FWD_ROUTES = ("v1_bk32", "v1_bk64", "v2_bn64", "v2_bn128")
+_BWD_DATA_ROUTES = ("s2_fused", "v2", "v1_bk32", "v1_bk64")
+_BWD_WEIGHT_ROUTES = ("v2", "v1_fast", "v1_generic")
 
 
 def _stream():
@@ -130,6 +139,50 @@ def _stem_cols(x, stride, pad, R, S, CRSpad):
     return col, Ho, Wo
 
 
+def conv2d_fwd_route(N, H, W_, C, K, R, S, stride, pad):
+    """(route name, ksplit) conv2d_fwd takes for this geometry outside graph
+    capture: v1_bk32 | v1_bk64 | v2_bn64 | v2_bn128."""
+    Ho = (H + 2 * pad - R) // stride + 1
+    Wo = (W_ + 2 * pad - S) // stride + 1
+    ks = _lib.cilfw_conv2d_fwd_ksplit(N, C, K, R, S, Ho, Wo)
+    return _FWD_ROUTES[_lib.cilfw_conv2d_fwd_route(N, C, K, R, S, Ho, Wo,
+                                                   ks)], ks
+
+
+def conv2d_bwd_data_route(N, H, W_, C, K, R, S, stride):
+    """(route name, ksplit) conv2d_bwd_data takes for dx of shape (N,H,W_,C):
+    s2_fused | v2 | v1_bk32 | v1_bk64. A strided 1x1 is solved on its
+    subsampled stride-1 grid, exactly as conv2d_bwd_data does."""
+    if R == 1 and S == 1 and stride > 1:
+        H, W_, stride = (H - 1) // stride + 1, (W_ - 1) // stride + 1, 1
+    ks = _lib.cilfw_conv2d_bwd_data_ksplit(N, H, W_, C, K, R, S)
+    return _BWD_DATA_ROUTES[_lib.cilfw_conv2d_bwd_data_route(
+        N, H, W_, C, K, R, S, stride, ks)], ks
+
+
+def _stem_im2col_dw(C, K, R, S):
+    """7x7 stems (ImageNet): the per-element gather path measured 542 us on
+    the 224^2 stem dW; padded-im2col + flat fast-path GEMM is far cheaper
+    there (3x3 CIFAR stems measured better on the direct gather)."""
+    use_im2col = (os.environ.get("CILFW_STEM_IM2COL") == "1"
+                  or (R * S >= 25
+                      and os.environ.get("CILFW_STEM_IM2COL") != "0"))
+    return C < 16 and R * S > 1 and K % 16 == 0 and use_im2col
+
+
+def conv2d_bwd_weight_route(N, C, K, R, S, Ho, Wo, accum=False):
+    """(route name, nslices) conv2d_bwd_weight takes: v2 | v1_fast |
+    v1_generic. Tiny-C stems on the im2col route run the flat GEMM over the
+    padded (M, CRSpad) columns, which never accumulates in-kernel."""
+    if _stem_im2col_dw(C, K, R, S):
+        N, C, R, S, Ho, Wo = N * Ho * Wo, (C * R * S + 15) // 16 * 16, 1, 1, \
+            1, 1
+        accum = False
+    ns = _lib.cilfw_conv2d_bwd_weight_nslices(N, C, K, R, S, Ho, Wo)
+    return _BWD_WEIGHT_ROUTES[_lib.cilfw_conv2d_bwd_weight_route(
+        N, C, K, R, S, Ho, Wo, 1 if accum else 0)], ns
+
+
 def conv2d_fwd(x, w, stride, pad, want_bn_parts=False):
     """want_bn_parts: also produce per-M-block per-channel (sum, sumsq)
     partials of y in the conv epilogue — a following training-mode BN skips
@@ -168,7 +221,11 @@ def conv2d_fwd(x, w, stride, pad, want_bn_parts=False):
     ws = (torch.empty(ks * N * Ho * Wo * K, dtype=torch.float32,
                       device=x.device) if ks > 1 else None)
     parts = None
-    if want_bn_parts and ks == 1 and C % 8 == 0             and os.environ.get("CILFW_CONV_V2", "1") != "0"             and os.environ.get("CILFW_CONV_BN_FUSE", "1") != "0":
+    # the BN-statistics epilogue lives in the v2 kernels' ksplit==1 stores
+    if want_bn_parts and ks == 1 \
+            and _FWD_ROUTES[_lib.cilfw_conv2d_fwd_route(
+                N, C, K, R, S, Ho, Wo, ks)].startswith("v2_") \
+            and os.environ.get("CILFW_CONV_BN_FUSE", "1") != "0":
         gy = (N * Ho * Wo + 127) // 128
         parts = torch.empty(gy * 2 * K, dtype=torch.float32,
                             device=x.device)
@@ -267,13 +324,7 @@ def conv2d_bwd_weight(dy, x, stride, pad, R, S, out=None, accum=False):
     _bf16(x, "conv2d_bwd_weight.x")
     N, H, W_, C = x.shape
     _, Ho, Wo, K = dy.shape
-    # 7x7 stems (ImageNet): the per-element gather path measured 542 us on
-    # the 224^2 stem dW; padded-im2col + flat fast-path GEMM is far cheaper
-    # there (3x3 CIFAR stems measured better on the direct gather)
-    use_im2col = (os.environ.get("CILFW_STEM_IM2COL") == "1"
-                  or (R * S >= 25
-                      and os.environ.get("CILFW_STEM_IM2COL") != "0"))
-    if C < 16 and R * S > 1 and K % 16 == 0 and use_im2col:
+    if _stem_im2col_dw(C, K, R, S):
         CRS = C * R * S
         CRSpad = (CRS + 15) // 16 * 16
         col, _, _ = _stem_cols(x, stride, pad, R, S, CRSpad)

@@ -1632,29 +1632,30 @@ static int fwd_bm256_min_m() {
   return v;
 }
 
-void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
-                      int N, int H, int W, int C, int K, int R, int S,
-                      int stride, int pad, int Ho, int Wo, int ksplit,
-                      void* bn_parts, void* stream) {
-  ConvGeom g{N, H, W, C, K, R, S, stride, pad, pad, Ho, Wo,
-             0, 0, magic40(C), magic40(S)};
-  int M = N * Ho * Wo;
+// ------------------------------------------------------------ route codes
+// Small integers shared with cilfw/_hip_ops.py (which maps them to names) so
+// a test can assert which kernel a geometry selects. Each launcher below
+// branches on the SAME function that answers the query, so the two cannot
+// drift apart when a threshold is retuned.
+enum { FWD_V1_BK32 = 0, FWD_V1_BK64 = 1, FWD_V2_BN64 = 2, FWD_V2_BN128 = 3 };
+enum { BWDD_S2_FUSED = 0, BWDD_V2 = 1, BWDD_V1_BK32 = 2, BWDD_V1_BK64 = 3 };
+enum { BWDW_V2 = 0, BWDW_V1_FAST = 1, BWDW_V1_GENERIC = 2 };
+
+// BM=256 doubles MFMA-per-barrier when M is large enough to keep the grid
+// full (env-gated experiment; it runs the v1 BKT=32 kernel)
+static int fwd_bm(int M) { return (M >= fwd_bm256_min_m()) ? 256 : BM; }
+
+static int fwd_v2_eligible(int C) { return C % 8 == 0 && conv_v2_enabled(); }
+
+// have_zp: the zero page exists (always, outside graph capture)
+static int fwd_route(int M, int C, int K, int R, int S, int ksplit,
+                     int have_zp) {
   int CRS = C * R * S;
-  int fast_a = (C % 16 == 0);
-  // BM=256 doubles MFMA-per-barrier when M is large enough to keep the grid
-  // full; BKT=64 only when the grid is too small for BKT=32's 2x occupancy
-  int bm = (M >= fwd_bm256_min_m()) ? 256 : BM;
-  // (a BN=128 tile variant was tried and measured slower AND failed numerics
-  //  — removed; the template's NRC generalization remains at the validated 2)
-  int use64 = bm == BM && (CRS >= bk64_min_crs()) &&
-              (cdiv(M, BM) * cdiv(K, BN) * ksplit < bk64_max_blocks());
-  void* zp = (C % 8 == 0 && conv_v2_enabled()) ? zpage_ptr() : nullptr;
-  if (zp != nullptr && bm == BM) {
+  int bm = fwd_bm(M);
+  if (have_zp && fwd_v2_eligible(C) && bm == BM) {
     // all-glds 2-phase kernel (v2): BK=64, tr_b16 B operand. A 128-wide
     // N-tile (2x the MFMA per staged A-byte at 2 blocks/CU) for K >= 128
     // when the grid still fills the chip; env CILFW_CONV_V2_BN128=0 off.
-    int nk2 = cdiv(CRS, V2BK);
-    int ks2 = ksplit;
     static int bn128 = -1;
     if (bn128 < 0) {
       const char* e = getenv("CILFW_CONV_V2_BN128");
@@ -1671,38 +1672,62 @@ void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
     }
     int shape_ok = (R == 1 && S == 1) || (min3x3 >= 0 && M >= min3x3);
     if (bn128 && K % 128 == 0 && shape_ok &&
-        cdiv(M, BM) * cdiv(K, 128) * ks2 >= 256) {
-      dim3 grid2(cdiv(M, BM), cdiv(K, 128), ks2);
+        cdiv(M, BM) * cdiv(K, 128) * ksplit >= 256)
+      return FWD_V2_BN128;
+    return FWD_V2_BN64;
+  }
+  // BKT=64 only when the grid is too small for BKT=32's 2x occupancy
+  // (a BN=128 v1 tile variant was tried and measured slower AND failed
+  //  numerics — removed; the template's NRC generalization remains at the
+  //  validated 2)
+  int use64 = bm == BM && (CRS >= bk64_min_crs()) &&
+              (cdiv(M, BM) * cdiv(K, BN) * ksplit < bk64_max_blocks());
+  return use64 ? FWD_V1_BK64 : FWD_V1_BK32;
+}
+
+// which forward kernel cilfw_conv2d_fwd launches for this geometry
+int cilfw_conv2d_fwd_route(int N, int C, int K, int R, int S, int Ho, int Wo,
+                           int ksplit) {
+  return fwd_route(N * Ho * Wo, C, K, R, S, ksplit, 1);
+}
+
+void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
+                      int N, int H, int W, int C, int K, int R, int S,
+                      int stride, int pad, int Ho, int Wo, int ksplit,
+                      void* bn_parts, void* stream) {
+  ConvGeom g{N, H, W, C, K, R, S, stride, pad, pad, Ho, Wo,
+             0, 0, magic40(C), magic40(S)};
+  int M = N * Ho * Wo;
+  int CRS = C * R * S;
+  int fast_a = (C % 16 == 0);
+  void* zp = fwd_v2_eligible(C) ? zpage_ptr() : nullptr;
+  int route = fwd_route(M, C, K, R, S, ksplit, zp != nullptr);
+  if (route == FWD_V2_BN128 || route == FWD_V2_BN64) {
+    int nk2 = cdiv(CRS, V2BK);
+    int bn2 = route == FWD_V2_BN128 ? 128 : BN;
+    dim3 grid2(cdiv(M, BM), cdiv(K, bn2), ksplit);
+    float* parts = (float*)(ksplit > 1 ? nullptr : bn_parts);
+    if (route == FWD_V2_BN128)
       hipLaunchKernelGGL(conv2d_fwd_v2_kernel<128>, grid2, dim3(NTHREADS),
                          0, (hipStream_t)stream, (const bf16_t*)x,
                          (const bf16_t*)w, (bf16_t*)y, (float*)ws,
-                         (const bf16_t*)zp, g, M, CRS, nk2, ks2,
-                         (float*)(ks2 > 1 ? nullptr : bn_parts));
-      if (ks2 > 1) {
-        long len = (long)M * K;
-        hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                           dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                           dim3(NTHREADS), 0, (hipStream_t)stream,
-                           (float*)ws, (bf16_t*)y, ks2, len);
-      }
-      return;
-    }
-    dim3 grid2(cdiv(M, BM), cdiv(K, BN), ks2);
-    hipLaunchKernelGGL(conv2d_fwd_v2_kernel<BN>, grid2, dim3(NTHREADS), 0,
-                       (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)w, (bf16_t*)y, (float*)ws,
-                       (const bf16_t*)zp, g, M, CRS, nk2, ks2,
-                       (float*)(ks2 > 1 ? nullptr : bn_parts));
-    if (ks2 > 1) {
+                         (const bf16_t*)zp, g, M, CRS, nk2, ksplit, parts);
+    else
+      hipLaunchKernelGGL(conv2d_fwd_v2_kernel<BN>, grid2, dim3(NTHREADS), 0,
+                         (hipStream_t)stream, (const bf16_t*)x,
+                         (const bf16_t*)w, (bf16_t*)y, (float*)ws,
+                         (const bf16_t*)zp, g, M, CRS, nk2, ksplit, parts);
+    if (ksplit > 1) {
       long len = (long)M * K;
       hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
                          dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
                          dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                         (bf16_t*)y, ks2, len);
+                         (bf16_t*)y, ksplit, len);
     }
     return;
   }
-  int nk = cdiv(CRS, use64 ? 64 : 32);
+  int bm = fwd_bm(M);
+  int nk = cdiv(CRS, route == FWD_V1_BK64 ? 64 : 32);
   dim3 grid(cdiv(M, bm), cdiv(K, BN), ksplit);
 #define LAUNCH_FWD(BKT_, BM_)                                                 \
   do {                                                                        \
@@ -1717,10 +1742,10 @@ void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
                          (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y,      \
                          (float*)ws, g, M, CRS, nk, fast_a, ksplit);          \
   } while (0)
-  if (bm == 256)
-    LAUNCH_FWD(32, 256);
-  else if (use64)
+  if (route == FWD_V1_BK64)
     LAUNCH_FWD(64, 128);
+  else if (bm == 256)
+    LAUNCH_FWD(32, 256);
   else
     LAUNCH_FWD(32, 128);
 #undef LAUNCH_FWD
@@ -1759,15 +1784,44 @@ static int bnbwd_fuse_enabled() {
 // exact predicate for "bwd-data will take the v1 ksplit==1 path and can emit
 // BN-backward partials" — Python checks this before allocating the parts
 // buffer; the launcher re-checks and reports what it actually did
+static int bwd_data_v2_eligible(int M, int K, int stride) {
+  return K % 8 == 0 && stride <= 2 && conv_v2_enabled() &&
+         M >= conv_v2_bwd_minm();
+}
+
+// have_zp: the zero page exists (always, outside graph capture)
+static int bwd_data_route(int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int ksplit, int have_zp) {
+  int H2max = (H + 1) >> 1, W2max = (W + 1) >> 1;
+  int Mc = N * H2max * W2max;
+  // fused 4-class parity decomposition: grid.z = (hi%2, wi%2) class;
+  // small per-class grids fall back to the single zero-structured kernel
+  // (its ksplit fills the chip better there — measured)
+  if (stride == 2 && (R > 1 || S > 1) && K % 16 == 0 &&
+      cdiv(Mc, BM) * cdiv(C, BN) >= 128 &&
+      getenv("CILFW_NO_S2_FUSED") == nullptr)
+    return BWDD_S2_FUSED;
+  int M = N * H * W;
+  if (have_zp && bwd_data_v2_eligible(M, K, stride)) return BWDD_V2;
+  int use64 = (R * S * K >= bk64_min_crs()) &&
+              (cdiv(M, BM) * cdiv(C, BN) * ksplit < bk64_max_blocks());
+  return use64 ? BWDD_V1_BK64 : BWDD_V1_BK32;
+}
+
+// which bwd-data kernel cilfw_conv2d_bwd_data launches for this geometry
+int cilfw_conv2d_bwd_data_route(int N, int H, int W, int C, int K, int R,
+                                int S, int stride, int ksplit) {
+  return bwd_data_route(N, H, W, C, K, R, S, stride, ksplit, 1);
+}
+
 int cilfw_conv2d_bwd_data_can_fuse_bn(int N, int H, int W, int C, int K,
                                       int R, int S, int stride) {
   if (!bnbwd_fuse_enabled() || stride != 1) return 0;
-  int M = N * H * W;
-  if (K % 8 == 0 && conv_v2_enabled() && M >= conv_v2_bwd_minm())
-    return 0;  // v2 all-glds kernel has no BN epilogue (yet)
-  int RSK = R * S * K;
-  int nk = cdiv(RSK, 32);
-  return pick_ksplit(cdiv(M, BM) * cdiv(C, BN), nk) == 1;
+  int ks = pick_ksplit(cdiv(N * H * W, BM) * cdiv(C, BN),
+                       cdiv(R * S * K, 32));
+  // v2 all-glds kernel has no BN epilogue (yet)
+  int route = bwd_data_route(N, H, W, C, K, R, S, stride, ks, 1);
+  return (route == BWDD_V1_BK32 || route == BWDD_V1_BK64) && ks == 1;
 }
 
 int cilfw_conv2d_bwd_data_bn_gy(int N, int H, int W) {
@@ -1782,26 +1836,22 @@ int cilfw_conv2d_bwd_data(const void* dy, const void* w, void* dx, void* ws,
                           void* bn_parts, int bn_relu, void* stream) {
   ConvGeom g{N, H, W, C, K, R, S, stride, pad, pad, Ho, Wo,
              0, 0, magic40(K), magic40(S)};
-  int H2max = (H + 1) >> 1, W2max = (W + 1) >> 1;
-  int Mc = N * H2max * W2max;
-  if (stride == 2 && (R > 1 || S > 1) && K % 16 == 0 &&
-      cdiv(Mc, BM) * cdiv(C, BN) >= 128 &&
-      getenv("CILFW_NO_S2_FUSED") == nullptr) {
-    // fused 4-class parity decomposition: grid.z = (hi%2, wi%2) class;
-    // small per-class grids fall back to the single zero-structured kernel
-    // (its ksplit fills the chip better there — measured)
+  int M = N * H * W;
+  int RSK = R * S * K;
+  // the zero page is only needed (and only allocated) for v2 candidates
+  void* zp = bwd_data_v2_eligible(M, K, stride) ? zpage_ptr() : nullptr;
+  int route = bwd_data_route(N, H, W, C, K, R, S, stride, ksplit,
+                             zp != nullptr);
+  if (route == BWDD_S2_FUSED) {
+    int Mc = N * ((H + 1) >> 1) * ((W + 1) >> 1);
     dim3 grid(cdiv(Mc, BM), cdiv(C, BN), 4);
     hipLaunchKernelGGL((conv2d_bwd_data_s2_kernel<32>), grid, dim3(NTHREADS),
                        0, (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)w, (bf16_t*)dx, g);
     return 0;
   }
-  int M = N * H * W;
-  int RSK = R * S * K;
   int fast_a = (K % 16 == 0) && stride <= 2;  // FAST path shift-divides
-  void* zp = (K % 8 == 0 && stride <= 2 && conv_v2_enabled()
-              && M >= conv_v2_bwd_minm()) ? zpage_ptr() : nullptr;
-  if (zp != nullptr) {  // all-glds 2-phase kernel (v2)
+  if (route == BWDD_V2) {  // all-glds 2-phase kernel (v2)
     int nk2 = cdiv(RSK, V2BK);
     dim3 grid2(cdiv(M, BM), cdiv(C, BN), ksplit);
     hipLaunchKernelGGL(conv2d_bwd_data_v2_kernel, grid2, dim3(NTHREADS), 0,
@@ -1817,8 +1867,7 @@ int cilfw_conv2d_bwd_data(const void* dy, const void* w, void* dx, void* ws,
     }
     return 0;
   }
-  int use64 = (RSK >= bk64_min_crs()) &&
-              (cdiv(M, BM) * cdiv(C, BN) * ksplit < bk64_max_blocks());
+  int use64 = route == BWDD_V1_BK64;
   int nk = cdiv(RSK, use64 ? 64 : 32);
   dim3 grid(cdiv(M, BM), cdiv(C, BN), ksplit);
   // BN-backward partial-sum epilogue: only the ksplit==1 v1 path materializes
@@ -1865,9 +1914,9 @@ void cilfw_conv2d_bwd_data_sub(const void* dy, const void* w, void* dx,
   int M = N * H * W;
   int RSK = R * S * K;
   int fast_a = (K % 16 == 0);  // stride fixed at 1 here
-  void* zp = (K % 8 == 0 && conv_v2_enabled()
-              && M >= conv_v2_bwd_minm()) ? zpage_ptr() : nullptr;
-  if (zp != nullptr) {  // all-glds 2-phase kernel (v2)
+  void* zp = bwd_data_v2_eligible(M, K, 1) ? zpage_ptr() : nullptr;
+  int route = bwd_data_route(N, H, W, C, K, R, S, 1, ksplit, zp != nullptr);
+  if (route == BWDD_V2) {  // all-glds 2-phase kernel (v2)
     int nk2 = cdiv(RSK, V2BK);
     dim3 grid2(cdiv(M, BM), cdiv(C, BN), ksplit);
     hipLaunchKernelGGL(conv2d_bwd_data_v2_kernel, grid2, dim3(NTHREADS), 0,
@@ -1883,8 +1932,7 @@ void cilfw_conv2d_bwd_data_sub(const void* dy, const void* w, void* dx,
     }
     return;
   }
-  int use64 = (RSK >= bk64_min_crs()) &&
-              (cdiv(M, BM) * cdiv(C, BN) * ksplit < bk64_max_blocks());
+  int use64 = route == BWDD_V1_BK64;
   int nk = cdiv(RSK, use64 ? 64 : 32);
   dim3 grid(cdiv(M, BM), cdiv(C, BN), ksplit);
 #define LAUNCH_BWD_DATA_SUB(BKT_, FAST_)                                       \
@@ -1928,6 +1976,25 @@ int cilfw_conv2d_bwd_data_ksplit(int N, int H, int W, int C, int K, int R,
   return pick_ksplit(cdiv(M, BM) * cdiv(C, BN), nk);
 }
 
+static int bwd_weight_v2_eligible(int C, int K, int accum) {
+  return C % 8 == 0 && K % 8 == 0 && accum == 0 && conv_v2_enabled();
+}
+
+// have_zp: the zero page exists (always, outside graph capture)
+static int bwd_weight_route(int C, int K, int accum, int have_zp) {
+  if (have_zp && bwd_weight_v2_eligible(C, K, accum)) return BWDW_V2;
+  return (C % 8 == 0) ? BWDW_V1_FAST : BWDW_V1_GENERIC;
+}
+
+// which bwd-weight kernel cilfw_conv2d_bwd_weight launches; the spatial
+// geometry is part of the signature so a later M-dependent threshold does
+// not change the ABI (today only C, K and accum decide)
+int cilfw_conv2d_bwd_weight_route(int N, int C, int K, int R, int S, int Ho,
+                                  int Wo, int accum) {
+  (void)N; (void)R; (void)S; (void)Ho; (void)Wo;
+  return bwd_weight_route(C, K, accum, 1);
+}
+
 void cilfw_conv2d_bwd_weight(const void* dy, const void* x, const void* mt,
                              void* dw, void* ws, int N, int H, int W, int C,
                              int K, int R, int S, int stride, int pad, int Ho,
@@ -1946,9 +2013,9 @@ void cilfw_conv2d_bwd_weight(const void* dy, const void* x, const void* mt,
   slice_len = cdiv(slice_len, WBK) * WBK;
   int fast_a = (C % 8 == 0);
   dim3 grid(cdiv(CRS, WBM), cdiv(K, BN), nslices);
-  void* zp = (fast_a && K % 8 == 0 && accum == 0 && conv_v2_enabled())
-                 ? zpage_ptr() : nullptr;
-  if (zp != nullptr) {  // all-glds 2-phase kernel (v2)
+  void* zp = bwd_weight_v2_eligible(C, K, accum) ? zpage_ptr() : nullptr;
+  int route = bwd_weight_route(C, K, accum, zp != nullptr);
+  if (route == BWDW_V2) {  // all-glds 2-phase kernel (v2)
     hipLaunchKernelGGL(conv2d_bwd_weight_v2_kernel, grid, dim3(NTHREADS), 0,
                        (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)x, (float*)ws, (const bf16_t*)zp, g,
@@ -1960,7 +2027,7 @@ void cilfw_conv2d_bwd_weight(const void* dy, const void* x, const void* mt,
                        (float*)dw, nslices, len2, accum);
     return;
   }
-  if (fast_a)
+  if (route == BWDW_V1_FAST)
     hipLaunchKernelGGL(conv2d_bwd_weight_kernel<true>, grid, dim3(NTHREADS),
                        0, (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)x, (float*)ws, g, M, CRS, slice_len,
