@@ -68,6 +68,7 @@ _PROTOS = {
     "cilfw_herding_select": [c_vp] * 3 + [c_i] * 3 + [c_vp],
     "cilfw_herding_select_batch": [c_vp] * 6 + [c_i] * 3 + [c_vp],
     "cilfw_crop_resize": [c_vp] * 7 + [c_i] * 7 + [c_vp],
+    "cilfw_crop_resize_ragged": [c_vp] * 9 + [c_i] * 5 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -728,6 +729,56 @@ def crop_resize(src, idx, params, flip, out_size, mean255, std255, dtype):
                            c_i(N), c_i(Hs), c_i(Ws), c_i(C), c_i(S),
                            c_i(_CROP_RESIZE_MODES[dtype]), _stream())
     _check("crop_resize")
+    return out
+
+
+def crop_resize_ragged(pool, offsets, hw, channels, idx, params, flip,
+                       out_size, mean255, std255, dtype):
+    """crop_resize over a ragged source (csrc/data.hip): pool uint8 flat
+    bytes; offsets int64 (M,) byte offset of image m; hw int32 (M,2) = (H, W);
+    image m is H*W*C contiguous HWC bytes. idx int64 (N,); the rest as
+    crop_resize. The tables live on the device, so offsets[m] + H*W*C <=
+    pool.numel() and H*W*C < 2**31 are the store's construction-time checks
+    (RaggedImageStore), not per-call ones: checking here would sync."""
+    assert pool.dtype == torch.uint8 and pool.dim() == 1 \
+        and pool.is_contiguous()
+    dev = pool.device
+    C, S = int(channels), int(out_size)
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 \
+        and offsets.device == dev and offsets.is_contiguous()
+    M = offsets.shape[0]
+    assert hw.dtype == torch.int32 and hw.shape == (M, 2) \
+        and hw.device == dev and hw.is_contiguous()
+    assert 1 <= C <= 4 and M >= 1 and S >= 1
+    assert S * S * C < 2 ** 31
+    assert idx is not None and idx.dtype == torch.int64 and idx.dim() == 1 \
+        and idx.device == dev
+    idx = idx.contiguous()
+    N = idx.shape[0]
+    assert params.shape == (N, 4) and params.dtype == torch.float32 \
+        and params.device == dev
+    assert flip.shape == (N,) and flip.dtype == torch.uint8 \
+        and flip.device == dev
+    params = params.contiguous()
+    flip = flip.contiguous()
+    if mean255 is None:
+        assert std255 is None
+        dtype = torch.uint8
+    else:
+        assert dtype in (torch.float32, torch.bfloat16), \
+            f"crop_resize_ragged: normalized output is fp32 or bf16 " \
+            f"(got {dtype})"
+        assert mean255.device == dev and std255.device == dev
+        mean255 = mean255.to(torch.float32).reshape(-1).contiguous()
+        std255 = std255.to(torch.float32).reshape(-1).contiguous()
+        assert mean255.numel() == C and std255.numel() == C
+    out = torch.empty(N, S, S, C, dtype=dtype, device=dev)
+    assert out.data_ptr() % 16 == 0  # the kernel stores 16-byte vectors
+    _lib.cilfw_crop_resize_ragged(
+        _ptr(pool), _ptr(offsets), _ptr(hw), _ptr(idx), _ptr(params),
+        _ptr(flip), _ptr(mean255), _ptr(std255), _ptr(out), c_i(M), c_i(N),
+        c_i(C), c_i(S), c_i(_CROP_RESIZE_MODES[dtype]), _stream())
+    _check("crop_resize_ragged")
     return out
 
 

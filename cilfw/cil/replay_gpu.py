@@ -103,19 +103,36 @@ class DeviceReplayMirror:
     def __init__(self, device):
         self.device = device
         self._imgs = {}    # class -> uint8 (k,H,W,C) device tensor, ranked
+        #                    (path-backed datasets: a compact RaggedImageStore)
         self._labels = {}  # class -> int64 (k,) device tensor
         self._tasks = {}   # class -> int64 (k,) device tensor
 
+    @staticmethod
+    def _is_store(x):
+        from ..data.ragged_store import RaggedImageStore
+        return isinstance(x, RaggedImageStore)
+
+    def _paths_store(self, paths, workers=0):
+        from ..data.ragged_store import RaggedImageStore
+        return RaggedImageStore.from_paths(list(paths), self.device, workers,
+                                           log=False)
+
     def update(self, memory, task_images=None, task_id=0):
         """Ingest memory's last add(): gather new-class exemplars from the
-        device-resident ``task_images`` (uint8, aligned with the x passed to
+        device-resident ``task_images`` (uint8 tensor, or the RaggedImageStore
+        prefix of a path-backed task; aligned with the x passed to
         memory.add), then trim every class to the new quota."""
         for c, keep in memory.last_selection.items():
-            if task_images is not None:
+            if self._is_store(task_images):
+                # compact per-class store: device-to-device slice copies
+                self._imgs[c] = task_images.gather(np.asarray(keep))
+            elif task_images is not None:
                 idx = torch.as_tensor(np.ascontiguousarray(keep),
                                       dtype=torch.int64,
                                       device=task_images.device)
                 self._imgs[c] = task_images[idx].to(self.device)
+            elif memory._x[c].dtype == object:  # paths: decode the exemplars
+                self._imgs[c] = self._paths_store(memory._x[c])
             else:  # fallback: one H2D upload of the selected exemplars
                 self._imgs[c] = torch.from_numpy(
                     np.ascontiguousarray(memory._x[c])).to(self.device)
@@ -127,17 +144,37 @@ class DeviceReplayMirror:
             ).to(self.device)
         q = memory.last_quota
         for c in list(self._imgs):
-            self._imgs[c] = self._imgs[c][:q]
+            if self._is_store(self._imgs[c]):
+                # a prefix VIEW would keep the whole old pool alive: compact
+                if len(self._imgs[c]) > q:
+                    self._imgs[c] = self._imgs[c].gather(np.arange(q))
+            else:
+                self._imgs[c] = self._imgs[c][:q]
             self._labels[c] = self._labels[c][:q]
             self._tasks[c] = self._tasks[c][:q]
 
     @classmethod
-    def from_memory(cls, memory, device):
-        """Rebuild after checkpoint resume (one upload, then resident)."""
+    def from_memory(cls, memory, device, workers=0):
+        """Rebuild after checkpoint resume (one upload, then resident). A
+        path-backed memory decodes its exemplar files once, all classes in
+        one pass, then splits them into the per-class stores."""
         self = cls(device)
-        for c in sorted(memory._x):
-            self._imgs[c] = torch.from_numpy(
-                np.ascontiguousarray(memory._x[c])).to(device)
+        classes = sorted(memory._x)
+        ragged = bool(classes) and memory._x[classes[0]].dtype == object
+        if ragged:
+            from ..data.ragged_store import RaggedImageStore
+            every = RaggedImageStore.from_paths(
+                np.concatenate([memory._x[c] for c in classes]), device,
+                workers)
+            lo = 0
+        for c in classes:
+            if ragged:
+                k = len(memory._x[c])
+                self._imgs[c] = every.gather(np.arange(lo, lo + k))
+                lo += k
+            else:
+                self._imgs[c] = torch.from_numpy(
+                    np.ascontiguousarray(memory._x[c])).to(device)
             self._labels[c] = torch.from_numpy(
                 np.ascontiguousarray(memory._y[c]).astype(np.int64)).to(device)
             self._tasks[c] = torch.from_numpy(
@@ -148,10 +185,17 @@ class DeviceReplayMirror:
         return sum(v.shape[0] for v in self._labels.values())
 
     def get(self):
-        """(images_u8, labels, task_ids) device tensors, memory.get() order."""
+        """(images_u8, labels, task_ids) device tensors, memory.get() order;
+        images_u8 is a RaggedImageStore for a path-backed dataset."""
         classes = sorted(self._imgs)
         if not classes:
             raise ValueError("mirror is empty")
-        return (torch.cat([self._imgs[c] for c in classes]),
+        if self._is_store(self._imgs[classes[0]]):
+            from ..data.ragged_store import RaggedImageStore
+            imgs = RaggedImageStore.concat_all(
+                [self._imgs[c] for c in classes])
+        else:
+            imgs = torch.cat([self._imgs[c] for c in classes])
+        return (imgs,
                 torch.cat([self._labels[c] for c in classes]),
                 torch.cat([self._tasks[c] for c in classes]))

@@ -99,7 +99,11 @@ def get_args_parser():
     parser.add_argument("--gpu_data", action="store_true", default=False,
                         help="HBM-resident task data + on-device batch "
                              "assembly (crop/flip/normalize) — bypasses the "
-                             "Python DataLoader for array-backed datasets")
+                             "Python DataLoader for array-backed datasets "
+                             "and, at --input_size > 64, for ImageFolder "
+                             "trees (decoded once into a device-resident "
+                             "ragged store; CILFW_GPU_DATA_PATHS=0 keeps "
+                             "those on the host DataLoader)")
     parser.add_argument("--no_wa", action="store_true", default=False,
                         help="ablation: skip the weight-align step")
     parser.add_argument("--no_replay", action="store_true", default=False,

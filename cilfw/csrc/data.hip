@@ -45,17 +45,48 @@ DEV typename OutVec<MODE>::T out_cvt(float level, const float* mean255,
   return (typename OutVec<MODE>::T)f2bf(v);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(DNT)
-void crop_resize_kernel(const uint8_t* __restrict__ src,
-                        const int64_t* __restrict__ idx,
-                        const float* __restrict__ params,
-                        const uint8_t* __restrict__ flip,
-                        const float* __restrict__ mean255,
-                        const float* __restrict__ std255,
-                        typename OutVec<MODE>::T* __restrict__ out,
-                        int M, int N, int Hs, int Ws, int C, int S,
-                        long total) {
+// Source accessors. The kernel body is shared; what differs is where sample m
+// lives and how large it is. Dense: one [M,Hs,Ws,C] tensor, geometry uniform
+// (kernel constants after inlining). Ragged: a flat byte pool with per-image
+// byte offsets and (H, W); image m is H*W*C contiguous HWC bytes at
+// pool + offsets[m].
+struct DenseSrc {
+  const uint8_t* src;
+  int Hs, Ws;
+  long img_elems;
+  DEV void sample(long m, const uint8_t*& base, int& H, int& W) const {
+    base = src + m * img_elems;
+    H = Hs;
+    W = Ws;
+  }
+};
+
+struct RaggedSrc {
+  const uint8_t* pool;
+  const int64_t* offsets;
+  const int* hw;
+  DEV void sample(long m, const uint8_t*& base, int& H, int& W) const {
+    base = pool + offsets[m];
+    H = hw[2 * m];
+    W = hw[2 * m + 1];
+  }
+};
+
+// A lane's 16 bytes may straddle two samples. With a ragged source those two
+// samples differ in H, W and base, so EVERYTHING derived from the image is
+// per-sample state reloaded at the new_sample transition: the clamp limits
+// (ymax, xmax, Hs, Ws) and the row stride here, and - because a new sample
+// always starts a new row and a new pixel - the row pointers and x offsets
+// right below it in the same iteration.
+template <int MODE, class Src>
+DEV void crop_resize_body(const Src& source,
+                          const int64_t* __restrict__ idx,
+                          const float* __restrict__ params,
+                          const uint8_t* __restrict__ flip,
+                          const float* __restrict__ mean255,
+                          const float* __restrict__ std255,
+                          typename OutVec<MODE>::T* __restrict__ out,
+                          int M, int C, int S, long total) {
 #pragma clang fp contract(off)
   typedef typename OutVec<MODE>::T T;
   constexpr int V = OutVec<MODE>::V;
@@ -72,14 +103,13 @@ void crop_resize_kernel(const uint8_t* __restrict__ src,
   int j = q / C;
   int c = q - j * C;
 
-  const long img_elems = (long)Hs * Ws * C;
-  const int row_elems = Ws * C;
-  const float ymax = (float)(Hs - 1), xmax = (float)(Ws - 1);
-
   float oy = 0.f, ox = 0.f, sy = 0.f, sx = 0.f, ty = 0.f, tx = 0.f;
   bool fl = false;
-  const uint8_t* base = src;
-  const uint8_t *r0 = src, *r1 = src;  // rows y0 / y1 of the current sample
+  // per-sample source state
+  const uint8_t* base = nullptr;
+  int Hs = 1, Ws = 1, row_elems = 0;
+  float ymax = 0.f, xmax = 0.f;
+  const uint8_t *r0 = nullptr, *r1 = nullptr;  // rows y0 / y1 of the sample
   int xo0 = 0, xo1 = 0;                // element offsets of x0 / x1 in a row
   bool new_sample = true, new_row = true, new_pix = true;
 
@@ -93,7 +123,10 @@ void crop_resize_kernel(const uint8_t* __restrict__ src,
         fl = flip[n] != 0;
         long m = idx ? (long)idx[n] : (long)n;
         m = m < 0 ? 0 : (m > M - 1 ? M - 1 : m);  // never read outside src
-        base = src + m * img_elems;
+        source.sample(m, base, Hs, Ws);
+        row_elems = Ws * C;
+        ymax = (float)(Hs - 1);
+        xmax = (float)(Ws - 1);
         new_sample = false;
       }
       if (new_row) {
@@ -147,6 +180,39 @@ void crop_resize_kernel(const uint8_t* __restrict__ src,
   }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(DNT)
+void crop_resize_kernel(const uint8_t* __restrict__ src,
+                        const int64_t* __restrict__ idx,
+                        const float* __restrict__ params,
+                        const uint8_t* __restrict__ flip,
+                        const float* __restrict__ mean255,
+                        const float* __restrict__ std255,
+                        typename OutVec<MODE>::T* __restrict__ out,
+                        int M, int N, int Hs, int Ws, int C, int S,
+                        long total) {
+  DenseSrc source = {src, Hs, Ws, (long)Hs * Ws * C};
+  crop_resize_body<MODE>(source, idx, params, flip, mean255, std255, out, M,
+                         C, S, total);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(DNT)
+void crop_resize_ragged_kernel(const uint8_t* __restrict__ pool,
+                               const int64_t* __restrict__ offsets,
+                               const int* __restrict__ hw,
+                               const int64_t* __restrict__ idx,
+                               const float* __restrict__ params,
+                               const uint8_t* __restrict__ flip,
+                               const float* __restrict__ mean255,
+                               const float* __restrict__ std255,
+                               typename OutVec<MODE>::T* __restrict__ out,
+                               int M, int C, int S, long total) {
+  RaggedSrc source = {pool, offsets, hw};
+  crop_resize_body<MODE>(source, idx, params, flip, mean255, std255, out, M,
+                         C, S, total);
+}
+
 extern "C" {
 
 // src uint8 [M,Hs,Ws,C]; idx int64 [N] or null (identity, N == M);
@@ -172,6 +238,34 @@ void cilfw_crop_resize(const void* src, const void* idx, const void* params,
   else if (out_mode == OUT_F32) CILFW_CR_LAUNCH(OUT_F32);
   else CILFW_CR_LAUNCH(OUT_BF16);
 #undef CILFW_CR_LAUNCH
+}
+
+// The same over a ragged source: pool uint8 flat bytes; offsets int64 [M]
+// (byte offset of image m, honoured as given); hw int32 [M,2] = (H, W); image
+// m is H*W*C contiguous HWC bytes. idx int64 [N] (required); the rest as
+// cilfw_crop_resize. The caller guarantees offsets[m] + H*W*C <= pool size
+// and H*W*C < 2^31 for every m (checked once where the pool is built).
+void cilfw_crop_resize_ragged(const void* pool, const void* offsets,
+                              const void* hw, const void* idx,
+                              const void* params, const void* flip,
+                              const void* mean255, const void* std255,
+                              void* out, int M, int N, int C, int S,
+                              int out_mode, void* stream) {
+  long total = (long)N * S * S * C;
+  if (total <= 0 || M <= 0) return;
+#define CILFW_CRR_LAUNCH(MODE)                                                \
+  hipLaunchKernelGGL(                                                         \
+      crop_resize_ragged_kernel<MODE>,                                        \
+      dim3((unsigned)((total + (long)DNT * OutVec<MODE>::V - 1) /             \
+                      ((long)DNT * OutVec<MODE>::V))),                        \
+      dim3(DNT), 0, (hipStream_t)stream, (const uint8_t*)pool,                \
+      (const int64_t*)offsets, (const int*)hw, (const int64_t*)idx,           \
+      (const float*)params, (const uint8_t*)flip, (const float*)mean255,      \
+      (const float*)std255, (OutVec<MODE>::T*)out, M, C, S, total)
+  if (out_mode == OUT_U8) CILFW_CRR_LAUNCH(OUT_U8);
+  else if (out_mode == OUT_F32) CILFW_CRR_LAUNCH(OUT_F32);
+  else CILFW_CRR_LAUNCH(OUT_BF16);
+#undef CILFW_CRR_LAUNCH
 }
 
 }  // extern "C"

@@ -283,6 +283,85 @@ def resize_params(N, Hs, Ws, S, device):
             torch.zeros(N, dtype=torch.uint8, device=device))
 
 
+# Per-image variants for ops.crop_resize_ragged: ``hw`` is the int (N,2)
+# tensor of each output sample's own source (H, W), gathered on the device
+# from a RaggedImageStore's table. Same rules as above, row by row, no host
+# sync.
+
+def rrc_params_ragged(hw, S, generator, scale=(0.08, 1.0),
+                      ratio=(3 / 4, 4 / 3)):
+    """rrc_params with a per-sample source size. Draws from ``generator`` in
+    the same order and shapes as rrc_params, and evaluates the same fp32
+    expressions, so with every row equal to (Hs, Ws) and the same seed it
+    returns exactly rrc_params(N, Hs, Ws, S, ...)."""
+    device = hw.device
+    N = hw.shape[0]
+
+    def rand(*shape):
+        return torch.rand(*shape, device=device, generator=generator)
+
+    Hi, Wi = hw[:, 0].long(), hw[:, 1].long()
+    Hs, Ws = Hi.float(), Wi.float()
+    area = (Hi * Wi).float().view(N, 1) \
+        * (scale[0] + rand(N, 10) * (scale[1] - scale[0]))
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    ar = torch.exp(lo + rand(N, 10) * (hi - lo))
+    w = torch.sqrt(area * ar).round().clamp_min(1.0)
+    h = torch.sqrt(area / ar).round().clamp_min(1.0)
+    ok = (w <= Ws.view(N, 1)) & (h <= Hs.view(N, 1))
+    first = ok.float().argmax(dim=1, keepdim=True)  # first fitting candidate
+    fits = ok.any(dim=1)
+    side_i = torch.minimum(Hi, Wi)
+    side = side_i.float()
+    w = torch.where(fits, w.gather(1, first).squeeze(1), side)
+    h = torch.where(fits, h.gather(1, first).squeeze(1), side)
+    y = torch.minimum((rand(N) * (Hs - h + 1)).floor(), Hs - h)
+    x = torch.minimum((rand(N) * (Ws - w + 1)).floor(), Ws - w)
+    y = torch.where(fits, y, torch.div(Hi - side_i, 2,
+                                       rounding_mode="floor").float())
+    x = torch.where(fits, x, torch.div(Wi - side_i, 2,
+                                       rounding_mode="floor").float())
+    flip = (rand(N) < 0.5).to(torch.uint8)
+    return _box_params(y, x, h, w, S), flip
+
+
+def eval_params_ragged(hw, S):
+    """eval_params with a per-sample source size, computed in float64 (what
+    the scalar rule's Python floats are) and cast to fp32 last: row n is
+    bitwise the row eval_params(1, H_n, W_n, S, ...) produces."""
+    N = hw.shape[0]
+    R = int(256 / 224 * S)
+    Hi, Wi = hw[:, 0].long(), hw[:, 1].long()
+    H, W = Hi.double(), Wi.double()
+    short_i = torch.minimum(Hi, Wi)
+    # resize branch (short != R)
+    Z = (H * (R / short_i.double())).round().clamp_min(float(R))
+    den = (Z - 1).clamp_min(1.0)
+    sy, sx = (H - 1) / den, (W - 1) / den
+    off = torch.div(Z.long() - S, 2, rounding_mode="floor").double()
+    resized = torch.stack([off * sy, off * sx, sy, sx], dim=1)
+    # short == R: no resize, scale exactly 1
+    one = torch.ones_like(H)
+    plain = torch.stack(
+        [torch.div(Hi - S, 2, rounding_mode="floor").double(),
+         torch.div(Wi - S, 2, rounding_mode="floor").double(), one, one],
+        dim=1)
+    params = torch.where((short_i != R).view(N, 1), resized, plain)
+    return (params.float().contiguous(),
+            torch.zeros(N, dtype=torch.uint8, device=hw.device))
+
+
+def resize_params_ragged(hw, S):
+    """resize_params with a per-sample source size (float64, cast last)."""
+    N = hw.shape[0]
+    d = float(max(S - 1, 1))
+    H, W = hw[:, 0].double(), hw[:, 1].double()
+    zero = torch.zeros_like(H)
+    params = torch.stack([zero, zero, (H - 1) / d, (W - 1) / d], dim=1)
+    return (params.float().contiguous(),
+            torch.zeros(N, dtype=torch.uint8, device=hw.device))
+
+
 DEVICE_OPS = [autocontrast, equalize, invert, rotate, posterize, solarize,
               solarize_add, color, contrast, brightness, sharpness, shear_x,
               shear_y, translate_x, translate_y]

@@ -15,6 +15,13 @@ contract, from sources of any stored size. Those are ONE fused HIP launch per
 batch (``ops.crop_resize``, csrc/data.hip): gather -> bilinear resample ->
 flip -> quantize -> normalize straight from the resident uint8 tensor.
 
+Path-backed tasksets (ImageFolder trees; ``x`` is an object array of file
+paths) take the resampling modes too: the files are decoded once into a
+``RaggedImageStore`` (ragged_store.py: flat uint8 pool + per-image offset /
+size tables, full stored resolution) and every batch is one
+``ops.crop_resize_ragged`` launch with per-image geometry. ``crop_mode="pad"``
+needs a common stored size and is refused for them.
+
 Sharding is the torch-DistributedSampler contract via the single shared
 implementation ``cilfw.data.sampler.compute_shard`` (same seed+epoch
 permutation on every rank, pad-by-repetition, rank-strided slice).
@@ -36,19 +43,50 @@ class GpuTaskLoader:
     def __init__(self, taskset, batch_size, device, mean, std, world=1, rank=0,
                  shuffle=True, seed=0, augment=True, drop_last=True,
                  dtype=torch.bfloat16, pad=4, extra=None, aug_pipeline=None,
-                 crop_mode="pad", out_size=None):
-        assert taskset.x.dtype == np.uint8, \
-            "GpuTaskLoader needs array-backed images (not lazy paths)"
-        images = torch.from_numpy(np.ascontiguousarray(taskset.x)).to(device)
+                 crop_mode="pad", out_size=None, workers=0, store=None):
+        # path-backed taskset (ImageFolder trees): the images are decoded
+        # once into a RaggedImageStore (ragged_store.py) and every batch is
+        # ops.crop_resize_ragged of it. ``store`` hands in an already built
+        # store of exactly taskset's images instead of decoding them again.
+        self.ragged = taskset.x.dtype == object
+        assert self.ragged or taskset.x.dtype == np.uint8, \
+            "GpuTaskLoader needs uint8 array-backed images or image paths"
         labels = torch.from_numpy(
             np.ascontiguousarray(taskset.y).astype(np.int64)).to(device)
-        self.n_task = images.shape[0]
-        if extra is not None:
-            ex_imgs, ex_labels = extra[0], extra[1]
-            assert ex_imgs.dtype == torch.uint8
-            images = torch.cat([images, ex_imgs.to(device)])
-            labels = torch.cat([labels, ex_labels.to(device,
-                                                     torch.int64)])
+        if self.ragged:
+            from .ragged_store import RaggedImageStore
+            if crop_mode not in ("rrc", "eval", "resize"):
+                raise ValueError(
+                    f"GpuTaskLoader: path-backed images have no common "
+                    f"stored size, so crop_mode must be 'rrc', 'eval' or "
+                    f"'resize' (got {crop_mode!r}); 'pad' needs an "
+                    f"array-backed dataset")
+            assert out_size is not None, "path-backed images need out_size"
+            ex_store = None
+            if extra is not None:
+                ex_store = extra[0]
+                assert isinstance(ex_store, RaggedImageStore), \
+                    "replay for a path-backed taskset is a RaggedImageStore"
+            if store is not None:
+                assert len(store) == len(taskset.x)
+                images = store if ex_store is None else \
+                    RaggedImageStore.concat(store, ex_store)
+            else:
+                images = RaggedImageStore.from_paths(
+                    taskset.x, device, workers, append=ex_store)
+            self.n_task = len(taskset.x)
+            if extra is not None:
+                labels = torch.cat([labels, extra[1].to(device, torch.int64)])
+        else:
+            images = torch.from_numpy(
+                np.ascontiguousarray(taskset.x)).to(device)
+            self.n_task = images.shape[0]
+            if extra is not None:
+                ex_imgs, ex_labels = extra[0], extra[1]
+                assert ex_imgs.dtype == torch.uint8
+                images = torch.cat([images, ex_imgs.to(device)])
+                labels = torch.cat([labels, ex_labels.to(device,
+                                                         torch.int64)])
         self.images = images
         self.labels = labels
         self.batch_size = batch_size
@@ -112,6 +150,39 @@ class GpuTaskLoader:
                                         self.device)
         return self._param_cache[key]
 
+    def _resample_params_ragged(self, idx, g):
+        """(params, flip) rows for ops.crop_resize_ragged: the same rules
+        with each sample's own (H, W), gathered from the store's table on the
+        device. The generator draws are those of _resample_params."""
+        from .device_augment import (eval_params_ragged,
+                                     resize_params_ragged, rrc_params_ragged)
+        mode = self.crop_mode
+        if mode == "rrc" and not self.augment:
+            mode = "eval"
+        if mode == "rrc":
+            return rrc_params_ragged(self.images.hw[idx], self.out_size, g)
+        if mode not in self._param_cache:  # constant per image: build once
+            fn = eval_params_ragged if mode == "eval" else \
+                resize_params_ragged
+            self._param_cache[mode] = fn(self.images.hw, self.out_size)[0]
+        return (self._param_cache[mode][idx],
+                torch.zeros(idx.shape[0], dtype=torch.uint8,
+                            device=self.device))
+
+    def _crop_resize(self, idx, g, *norm):
+        """One fused launch for samples ``idx``: dense or ragged source."""
+        if self.ragged:
+            from ..ops import crop_resize_ragged
+            params, flip = self._resample_params_ragged(idx, g)
+            st = self.images
+            return crop_resize_ragged(st.pool, st.offsets, st.hw,
+                                      st.channels, idx, params, flip,
+                                      self.out_size, *norm)
+        from ..ops import crop_resize
+        params, flip = self._resample_params(idx.shape[0], g)
+        return crop_resize(self.images, idx, params, flip, self.out_size,
+                           *norm)
+
     def __iter__(self):
         shard = self._shard_indices()
         g = torch.Generator(device=self.device)
@@ -119,8 +190,6 @@ class GpuTaskLoader:
         nb = len(self)
         aug = self.aug_pipeline if self.augment else None
         resample = self.crop_mode != "pad"
-        if resample:
-            from ..ops import crop_resize
         aug_imgs = None
         if aug is not None and (aug.enabled or aug.color_jitter > 0):
             # EPOCH-level batched RandAugment + jitter over the whole shard:
@@ -137,10 +206,7 @@ class GpuTaskLoader:
             outs = []
             for c0 in range(0, shard.shape[0], 4096):
                 if resample:
-                    sel = shard[c0:c0 + 4096]
-                    params, flip = self._resample_params(sel.shape[0], g)
-                    chunk = crop_resize(self.images, sel, params, flip,
-                                        self.out_size)
+                    chunk = self._crop_resize(shard[c0:c0 + 4096], g)
                 else:
                     chunk = self.images[shard[c0:c0 + 4096]]
                 outs.append(aug(chunk, g).to(torch.uint8))
@@ -150,10 +216,8 @@ class GpuTaskLoader:
             idx = shard[b * self.batch_size:(b + 1) * self.batch_size]
             if resample and aug_imgs is None:
                 # one fused launch: resident uint8 -> normalized dtype
-                params, flip = self._resample_params(idx.shape[0], g)
-                imgs = crop_resize(self.images, idx, params, flip,
-                                   self.out_size, self.mean.view(-1),
-                                   self.std.view(-1), self.dtype)
+                imgs = self._crop_resize(idx, g, self.mean.view(-1),
+                                         self.std.view(-1), self.dtype)
             else:
                 if aug_imgs is not None:
                     imgs = aug_imgs[b * self.batch_size:

@@ -58,9 +58,19 @@ def _crop_modes(args):
 def _gpu_data_active(args, device, dataset):
     """--gpu_data engages for array-backed datasets on cuda devices; the env
     override CILFW_GPU_DATA_ON_CPU=1 lets tests exercise the same loader /
-    device-replay wiring on CPU (GpuTaskLoader is pure torch index ops)."""
+    device-replay wiring on CPU (GpuTaskLoader is pure torch index ops).
+    Path-backed datasets (ImageFolder trees) engage too at large inputs: the
+    files are decoded once into a device-resident RaggedImageStore.
+    CILFW_GPU_DATA_PATHS=0 keeps them on the host DataLoader."""
     import os
-    if not args.gpu_data or dataset.x.dtype != np.uint8:
+    if not args.gpu_data:
+        return False
+    if dataset.x.dtype == object:
+        from .data.datasets import Image
+        if args.input_size <= 64 or Image is None \
+                or os.environ.get("CILFW_GPU_DATA_PATHS") == "0":
+            return False
+    elif dataset.x.dtype != np.uint8:
         return False
     return (str(device).startswith("cuda")
             or os.environ.get("CILFW_GPU_DATA_ON_CPU") == "1")
@@ -276,17 +286,20 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
 
 
 @torch.no_grad()
-def extract_task_features(model, dataset, device, args):
+def extract_task_features(model, dataset, device, args, store=None):
     """Unshuffled, NON-distributed feature pass over the full task set — the
     reference runs this replicated on every rank (template.py:292-299); herding is
-    deterministic so the resulting memory is rank-identical."""
+    deterministic so the resulting memory is rank-identical. ``store``: the
+    already resident RaggedImageStore of a path-backed ``dataset`` (the train
+    loader's), so its files are not decoded a second time."""
     model.eval()
     dtype = compute_dtype(args)
     if _gpu_data_active(args, device, dataset):
         mean, std = DATASET_STATS[getattr(args, "_stats_key", "synthetic")]
         loader = GpuTaskLoader(dataset, args.batch_size, device, mean, std,
                                shuffle=False, augment=False, drop_last=False,
-                               dtype=dtype, **_crop_modes(args)[1])
+                               dtype=dtype, workers=args.workers,
+                               store=store, **_crop_modes(args)[1])
     else:
         # un-augmented features on the CPU path too (the device path always
         # extracts with augment=False; advisor round-1 flagged the mismatch)
@@ -395,7 +408,7 @@ def _run_tasks(args, device, watchdog):
                 if replay_mirror is None:  # resumed run: one rebuild upload
                     from .cil.replay_gpu import DeviceReplayMirror
                     replay_mirror = DeviceReplayMirror.from_memory(
-                        memory, device)
+                        memory, device, workers=args.workers)
                 assert len(replay_mirror) == len(memory), \
                     "device replay mirror out of sync with rehearsal memory"
                 extra = replay_mirror.get()
@@ -426,12 +439,12 @@ def _run_tasks(args, device, watchdog):
                 world=world, rank=rank, shuffle=True, seed=args.seed,
                 augment=not args.no_aug, drop_last=True,
                 dtype=compute_dtype(args), extra=extra, aug_pipeline=aug,
-                **_crop_modes(args)[0])
+                workers=args.workers, **_crop_modes(args)[0])
             val_loader = GpuTaskLoader(
                 dataset_val, args.batch_size, device, mean, std,
                 world=world, rank=rank, shuffle=False, augment=False,
                 drop_last=False, dtype=compute_dtype(args),
-                **_crop_modes(args)[1])
+                workers=args.workers, **_crop_modes(args)[1])
         else:
             train_sampler = DistributedSampler(dataset_train, world, rank,
                                                shuffle=True, seed=args.seed)
@@ -467,7 +480,11 @@ def _run_tasks(args, device, watchdog):
         if compute_dtype(args) == torch.bfloat16:
             teacher.cast_compute_weights_(torch.bfloat16)
 
-        features = extract_task_features(model, dataset_train, device, args)
+        task_store = None
+        if use_gpu_data and getattr(train_loader, "ragged", False):
+            task_store = train_loader.images[:train_loader.n_task]
+        features = extract_task_features(model, dataset_train, device, args,
+                                         store=task_store)
         rx, ry, rt = dataset_train.get_raw_samples()
         memory.add(rx, ry, rt, features)
         if use_device_replay:

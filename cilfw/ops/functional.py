@@ -847,3 +847,51 @@ def crop_resize(src_u8, idx, params, flip, out_size, mean255=None,
                                  mean255, std255, dtype)
     return crop_resize_reference(src_u8, idx, params, flip, out_size,
                                  mean255, std255, dtype)
+
+
+def crop_resize_ragged_reference(pool, offsets, hw, channels, idx, params,
+                                 flip, out_size, mean255=None, std255=None,
+                                 dtype=None):
+    """Pure-torch oracle of crop_resize over a ragged source: output sample n
+    views ``pool[o : o + H*W*C]`` (o = offsets[m], (H, W) = hw[m], m = idx[n]
+    clamped to [0, M-1]) as a (1, H, W, C) image and is crop_resize_reference
+    of it - the dense oracle applied per image, by construction. Reads the
+    tables on the host (it is an oracle and the CPU path, not a hot path)."""
+    C, S = int(channels), int(out_size)
+    M = offsets.shape[0]
+    N = idx.shape[0]
+    if mean255 is None:
+        odt = torch.uint8
+    else:
+        odt = dtype if dtype is not None else torch.float32
+    out = torch.empty(N, S, S, C, dtype=odt, device=pool.device)
+    ms = idx.clamp(0, M - 1).tolist() if N else []
+    offs, sizes = offsets.tolist(), hw.tolist()
+    for n, m in enumerate(ms):
+        H, W = sizes[m]
+        img = pool[offs[m]:offs[m] + H * W * C].view(1, H, W, C)
+        out[n] = crop_resize_reference(img, None, params[n:n + 1],
+                                       flip[n:n + 1], S, mean255, std255,
+                                       dtype)[0]
+    return out
+
+
+def crop_resize_ragged(pool, offsets, hw, channels, idx, params, flip,
+                       out_size, mean255=None, std255=None, dtype=None):
+    """crop_resize from a packed store of differently sized images: ``pool``
+    flat uint8 bytes, ``offsets`` int64 (M,) byte offset of image m, ``hw``
+    int32 (M,2) its (H, W), ``channels`` uniform; image m is H*W*C contiguous
+    HWC bytes. Gathers ``idx`` (int64 (N,)), resamples each image through its
+    own ``params`` row (+ flip) to out_size x out_size, uint8 levels or the
+    normalized ``dtype``. One HIP launch on a GPU, no allocation but the
+    output and no sync (capturable). Offsets / sizes are trusted: the store
+    that owns the pool validates them once (cilfw/data/ragged_store.py)."""
+    if use_hip(pool):
+        if mean255 is not None and dtype is None:
+            dtype = torch.float32
+        return ext().crop_resize_ragged(pool, offsets, hw, channels, idx,
+                                        params, flip, out_size, mean255,
+                                        std255, dtype)
+    return crop_resize_ragged_reference(pool, offsets, hw, channels, idx,
+                                        params, flip, out_size, mean255,
+                                        std255, dtype)
