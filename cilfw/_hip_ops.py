@@ -69,6 +69,8 @@ _PROTOS = {
     "cilfw_herding_select_batch": [c_vp] * 6 + [c_i] * 3 + [c_vp],
     "cilfw_crop_resize": [c_vp] * 7 + [c_i] * 7 + [c_vp],
     "cilfw_crop_resize_ragged": [c_vp] * 9 + [c_i] * 5 + [c_vp],
+    "cilfw_nme_prototypes": [c_vp] * 3 + [c_i] * 2 + [c_vp],
+    "cilfw_nme_topk": [c_vp] * 6 + [c_i] * 4 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -820,3 +822,64 @@ def herding_select_batch(feats_list, m_list):
         outs.append(order[o:o + m])
         o += m
     return outs
+
+
+# ------------------------------------------------------------------------- nme
+
+def _nme_f32(t, name, D=None):
+    assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous(), \
+        f"{name}: needs a contiguous 2-d fp32 tensor"
+    assert t.shape[1] % 4 == 0 and 4 <= t.shape[1] <= 4096, \
+        f"{name}: nme kernels support feature widths D % 4 == 0, " \
+        f"4 <= D <= 4096 (got D = {t.shape[1]})"
+    assert D is None or t.shape[1] == D, \
+        f"{name}: feature width {t.shape[1]} != {D}"
+    assert t.data_ptr() % 16 == 0  # the kernels load 16-byte vectors
+    return t
+
+
+def nme_prototypes(feats, seg_off):
+    """Unit-norm class prototypes (csrc/nme.hip). feats fp32 (n, D), rows
+    grouped by class; seg_off int32 (C+1,) device tensor of row offsets (the
+    caller has checked 0 = seg_off[0] < ... < seg_off[C] = n on the host:
+    checking here would sync). -> (C, D) fp32."""
+    _nme_f32(feats, "nme_prototypes.feats")
+    assert seg_off.dtype == torch.int32 and seg_off.dim() == 1 \
+        and seg_off.is_contiguous() and seg_off.device == feats.device \
+        and seg_off.numel() >= 2
+    C, D = seg_off.numel() - 1, feats.shape[1]
+    protos = torch.empty(C, D, dtype=torch.float32, device=feats.device)
+    _lib.cilfw_nme_prototypes(_ptr(feats), _ptr(seg_off), _ptr(protos),
+                              c_i(C), c_i(D), _stream())
+    _check("nme_prototypes")
+    return protos
+
+
+def nme_topk(feats, protos, maxk, targets=None):
+    """Fused normalize -> score -> running top-k (csrc/nme.hip): the (N, C)
+    score matrix is never materialized. -> (idx int32 (N, maxk), score fp32
+    (N, maxk), counts int64 (maxk,) | None); counts[k-1] = rows whose target
+    is within the top-k."""
+    _nme_f32(feats, "nme_topk.feats")
+    N, D = feats.shape
+    _nme_f32(protos, "nme_topk.protos", D)
+    C = protos.shape[0]
+    maxk = int(maxk)
+    assert protos.device == feats.device
+    assert 1 <= maxk <= min(8, C), \
+        f"nme_topk: maxk must be in 1..min(8, C) (got maxk={maxk}, C={C})"
+    assert N * maxk < 2 ** 31 and N < 2 ** 31 - 64
+    dev = feats.device
+    idx = torch.empty(N, maxk, dtype=torch.int32, device=dev)
+    score = torch.empty(N, maxk, dtype=torch.float32, device=dev)
+    counts = None
+    if targets is not None:
+        assert targets.dtype == torch.int64 and targets.shape == (N,) \
+            and targets.device == dev
+        targets = targets.contiguous()
+        counts = torch.empty(maxk, dtype=torch.int64, device=dev)
+    _lib.cilfw_nme_topk(_ptr(feats), _ptr(protos), _ptr(targets), _ptr(idx),
+                        _ptr(score), _ptr(counts), c_i(N), c_i(C), c_i(D),
+                        c_i(maxk), _stream())
+    _check("nme_topk")
+    return idx, score, counts

@@ -41,6 +41,9 @@ def save_task_checkpoint(path_dir, task_id, model, memory, acc1s, args,
                 "python": random.getstate(),
             },
         }
+        if getattr(args, "nme_eval", False):
+            # optional key: absent from checkpoints written without the flag
+            state["nme1s"] = list(getattr(args, "nme1s", []))
         torch.save(state, path)
     barrier()
     return path
@@ -61,6 +64,7 @@ def load_task_checkpoint(path, model, memory, args, restore_rng=True):
     args.nb_classes = state["nb_classes"]
     if state["class_order"] is not None:
         args.class_order = state["class_order"]
+    args.nme1s = list(state.get("nme1s", []))
     if restore_rng:
         torch.set_rng_state(state["rng"]["torch"])
         if torch.cuda.is_available() and state["rng"]["cuda"] is not None:

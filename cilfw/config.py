@@ -113,6 +113,11 @@ def get_args_parser():
                         help="with --gpu_data, source replay via host "
                              "add_samples instead of the HBM-resident "
                              "DeviceReplayMirror")
+    parser.add_argument("--nme_eval", action="store_true", default=False,
+                        help="after each task also evaluate with iCaRL's "
+                             "nearest-mean-of-exemplars classifier over the "
+                             "rehearsal memory (prints NME Acc@1/Acc@5 next "
+                             "to the linear head's; training is unchanged)")
     parser.add_argument("--max_tasks", default=0, type=int,
                         help="stop after N tasks (0 = all) — e.g. the "
                              "BASELINE config[0] 2-task plumbing oracle")

@@ -366,6 +366,8 @@ def _run_tasks(args, device, watchdog):
     teacher = None
     replay_mirror = None  # HBM-resident replay (DeviceReplayMirror)
     acc1s = []
+    nme_eval = getattr(args, "nme_eval", False)
+    nme1s = args.nme1s = []  # per-task NME top-1 history (--nme_eval)
     args.known_classes = 0
     start_task = 0
 
@@ -373,6 +375,7 @@ def _run_tasks(args, device, watchdog):
         state = load_task_checkpoint(args.resume, model, memory, args)
         model = model.to(device)
         acc1s = state["acc1s"]
+        nme1s = args.nme1s  # [] for checkpoints written without --nme_eval
         start_task = state["task_id"] + 1
         if start_task < len(scenario_train):
             teacher = model.copy().to(device)
@@ -498,6 +501,19 @@ def _run_tasks(args, device, watchdog):
                 task_images=train_loader.images[:train_loader.n_task],
                 task_id=task_id)
 
+        if nme_eval:
+            # iCaRL's nearest-mean-of-exemplars rule over the memory as just
+            # trimmed, next to the linear head's accuracy (cil/nme.py)
+            from .cil.nme import build_prototypes, evaluate_nme
+            protos = build_prototypes(
+                model, memory, device, args,
+                mirror=replay_mirror if use_device_replay else None)
+            nme1, _nme5 = evaluate_nme(model, protos, val_loader, device,
+                                       args)
+            nme1s.append(nme1)
+            print(f"task id = {task_id}  @NME1 = {nme1:.5f}, "
+                  f"nme1s = {nme1s}")
+
         engine.detach()
         args.known_classes += args.increment_per_task  # before snapshot: the
         # checkpoint records the post-task state so resume starts task t+1
@@ -508,4 +524,7 @@ def _run_tasks(args, device, watchdog):
 
     avg_inc_acc = sum(acc1s) / len(acc1s) if acc1s else 0.0
     print(f"average incremental accuracy = {avg_inc_acc:.5f}")
+    if nme_eval:
+        avg_inc_nme = sum(nme1s) / len(nme1s) if nme1s else 0.0
+        print(f"average incremental NME accuracy = {avg_inc_nme:.5f}")
     return acc1s

@@ -3,10 +3,12 @@ from .functional import (conv2d, batchnorm_act, batchnorm_add_relu, add_relu,
                          global_avg_pool, linear, cross_entropy, kd_loss, wa_loss,
                          accuracy, max_pool, crop_resize,
                          crop_resize_ragged, crop_resize_ragged_reference)
+from .nme import nme_prototypes, nme_topk
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
            "downsample_a",
            "global_avg_pool", "linear", "cross_entropy", "kd_loss", "wa_loss", "accuracy",
            "max_pool", "crop_resize", "crop_resize_ragged",
-           "crop_resize_ragged_reference", "have_ext"]
+           "crop_resize_ragged_reference", "nme_prototypes", "nme_topk",
+           "have_ext"]
