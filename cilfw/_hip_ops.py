@@ -71,6 +71,9 @@ _PROTOS = {
     "cilfw_crop_resize_ragged": [c_vp] * 9 + [c_i] * 5 + [c_vp],
     "cilfw_nme_prototypes": [c_vp] * 3 + [c_i] * 2 + [c_vp],
     "cilfw_nme_topk": [c_vp] * 6 + [c_i] * 4 + [c_vp],
+    "cilfw_pod_pool": [c_vp] * 2 + [c_i] * 4 + [c_vp],
+    "cilfw_pod_dist": [c_vp] * 5 + [c_i] * 2 + [c_vp],
+    "cilfw_pod_bwd": [c_vp] * 4 + [c_i] * 4 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -78,6 +81,8 @@ for _name, _args in _PROTOS.items():
     _fn.restype = None
 
 _lib.cilfw_conv2d_bwd_data.restype = c_i  # 1 = BN partials were emitted
+for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd"):
+    getattr(_lib, _name).restype = c_i  # 1 = shape refused, nothing launched
 
 for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_fwd_ksplit", 7),
@@ -87,7 +92,9 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_bwd_weight_nslices", 7),
                   ("cilfw_conv2d_fwd_route", 8),
                   ("cilfw_conv2d_bwd_data_route", 9),
-                  ("cilfw_conv2d_bwd_weight_route", 8)]:
+                  ("cilfw_conv2d_bwd_weight_route", 8),
+                  ("cilfw_pod_supported", 4),
+                  ("cilfw_pod_pool_groups", 2)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
@@ -883,3 +890,81 @@ def nme_topk(feats, protos, maxk, targets=None):
                         c_i(maxk), _stream())
     _check("nme_topk")
     return idx, score, counts
+
+
+# ------------------------------------------------------------------------- pod
+
+def _pod_map(t, name):
+    """bf16 NHWC map the POD kernels accept; the launchers in csrc/pod.hip
+    apply the same shape rule (cilfw_pod_supported) on the host."""
+    assert t.dim() == 4, f"{name}: needs an (N, H, W, C) map"
+    _bf16(t, name)
+    N, H, W_, C = t.shape
+    assert C % 8 == 0, \
+        f"{name}: POD kernels need C % 8 == 0 (got C = {C})"
+    assert 1 <= H <= 256 and 1 <= W_ <= 256, \
+        f"{name}: POD kernels support 1 <= H, W <= 256 (got {H} x {W_})"
+    assert N >= 1 and _lib.cilfw_pod_supported(N, H, W_, C) == 1
+    assert t.data_ptr() % 16 == 0  # the kernels load 16-byte vectors
+    return N, H, W_, C
+
+
+def pod_pool_groups(W_, C):
+    """Channel groups (of 8) one pod_pool block covers — for docs/benches."""
+    return _lib.cilfw_pod_pool_groups(c_i(W_), c_i(C))
+
+
+def pod_pool(a, out=None):
+    """(N, H, W, C) bf16 -> (N, H+W, C) fp32: row sums of squares r[h, c]
+    first, then column sums q[w, c] (csrc/pod.hip). ``out`` may be supplied
+    (every element is written)."""
+    N, H, W_, C = _pod_map(a, "pod_pool")
+    if out is None:
+        out = torch.empty(N, H + W_, C, dtype=torch.float32, device=a.device)
+    assert out.shape == (N, H + W_, C) and out.dtype == torch.float32 \
+        and out.is_contiguous() and out.device == a.device
+    rc = _lib.cilfw_pod_pool(_ptr(a), _ptr(out), c_i(N), c_i(H), c_i(W_),
+                             c_i(C), _stream())
+    assert rc == 0, "pod_pool: launcher refused the shape"
+    _check("pod_pool")
+    return out
+
+
+def pod_dist(vs, vt):
+    """Pooled student / teacher vectors (N, H+W, C) fp32 -> (loss 0-d fp32,
+    dist (N,) fp32, g_v (N, H+W, C) fp32 for upstream 1)."""
+    assert vs.shape == vt.shape and vs.dim() == 3
+    for t in (vs, vt):
+        assert t.dtype == torch.float32 and t.is_contiguous() \
+            and t.device == vs.device and t.data_ptr() % 16 == 0
+    N, L = vs.shape[0], vs.shape[1] * vs.shape[2]
+    assert L < 2 ** 31
+    gv = torch.empty_like(vs)
+    dist = torch.empty(N, dtype=torch.float32, device=vs.device)
+    loss = torch.empty(1, dtype=torch.float32, device=vs.device)
+    rc = _lib.cilfw_pod_dist(_ptr(vs), _ptr(vt), _ptr(gv), _ptr(dist),
+                             _ptr(loss), c_i(N), c_i(L), _stream())
+    assert rc == 0, "pod_dist: launcher refused the shape"
+    _check("pod_dist")
+    return loss[0], dist, gv
+
+
+def pod_bwd(a, gv, up, out=None):
+    """da = 2 a (g_v.r[h] + g_v.q[w]) * up, bf16 like ``a``. ``up``: 1-element
+    fp32 DEVICE tensor (read by the kernel: no host sync, graph-safe)."""
+    N, H, W_, C = _pod_map(a, "pod_bwd")
+    assert gv.shape == (N, H + W_, C) and gv.dtype == torch.float32 \
+        and gv.is_contiguous() and gv.device == a.device \
+        and gv.data_ptr() % 16 == 0
+    assert up.dtype == torch.float32 and up.numel() == 1 \
+        and up.device == a.device
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.dtype == torch.bfloat16 \
+        and out.is_contiguous() and out.device == a.device \
+        and out.data_ptr() % 16 == 0
+    rc = _lib.cilfw_pod_bwd(_ptr(a), _ptr(gv), _ptr(up), _ptr(out), c_i(N),
+                            c_i(H), c_i(W_), c_i(C), _stream())
+    assert rc == 0, "pod_bwd: launcher refused the shape"
+    _check("pod_bwd")
+    return out

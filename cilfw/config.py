@@ -72,6 +72,14 @@ def get_args_parser():
                              "(the reference parsed but never used this flag — "
                              "template.py:48; here it is honored)")
     parser.add_argument("--kd_temperature", default=2.0, type=float)
+    parser.add_argument("--lambda_pod", default=0.0, type=float,
+                        help="weight of PODNet's POD-spatial distillation "
+                             "over the backbone's stage outputs against the "
+                             "frozen teacher; scaled per task by "
+                             "sqrt(known_classes / increment) as in the "
+                             "paper (0 = off: no map is requested, no POD "
+                             "kernel runs; combine with --lambda_kd 0 for "
+                             "POD without logit KD)")
 
     # ---- cilfw-native flags (no reference counterpart) ----
     parser.add_argument("--class_order", default=None, type=str,

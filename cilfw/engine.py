@@ -188,19 +188,38 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                if (teacher is not None and str(device).startswith("cuda"))
                else None)
 
+    # POD-spatial over the stage outputs (ops/pod.py), the paper's weight:
+    # lambda_pod * sqrt(known / increment). Off (task 0 or lambda_pod == 0):
+    # no map is requested and no POD kernel is launched.
+    pod_w = 0.0
+    if teacher is not None and getattr(args, "lambda_pod", 0.0) > 0:
+        pod_w = args.lambda_pod * (known / args.increment_per_task) ** 0.5
+    use_pod = pod_w > 0
+
+    def teacher_fwd(inputs):
+        """-> (t_logits, t_maps | None); the maps stay referenced until the
+        POD term has read them, like t_logits until wa_loss."""
+        if use_pod:
+            t_logits, _, t_maps = teacher(inputs, return_maps=True)
+            return t_logits, t_maps
+        return teacher(inputs)[0], None
+
     def step_fn(inputs, targets, update=True):
         optimizer.zero_grad()
         if tstream is not None:
             tstream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(tstream), torch.no_grad():
-                t_logits, _ = teacher(inputs)
-        logits, _features = model(inputs)
+                t_logits, t_maps = teacher_fwd(inputs)
+        if use_pod:
+            logits, _features, maps = model(inputs, return_maps=True)
+        else:
+            logits, _features = model(inputs)
         if teacher is not None:
             if tstream is not None:
                 torch.cuda.current_stream().wait_stream(tstream)
             else:
                 with torch.no_grad():
-                    t_logits, _ = teacher(inputs)
+                    t_logits, t_maps = teacher_fwd(inputs)
             loss, loss_ce, loss_kd = ops.wa_loss(
                 logits, t_logits, targets, args.smooth,
                 args.kd_temperature, lambda_kd)
@@ -208,11 +227,16 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
             loss, loss_ce, loss_kd = ops.wa_loss(
                 logits, None, targets, args.smooth,
                 args.kd_temperature, lambda_kd)
+        loss_pod = None
+        if use_pod:
+            loss_pod = ops.pod_loss(maps, t_maps)
+            loss = loss + pod_w * loss_pod
+            loss_pod = loss_pod.detach()
         loss.backward()
         engine.finalize()
         if update:
             optimizer.step()
-        return logits, loss_ce, loss_kd, loss
+        return logits, loss_ce, loss_kd, loss, loss_pod
 
     import os as _os
     can_graph = (str(device).startswith("cuda") and not args.no_step_graph
@@ -248,19 +272,22 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                 # Drop the previous batch's autograd graph first: live loss/
                 # logits refs keep AccumulateGrad nodes pinned to the default
                 # stream, which breaks (segfaults) stream capture.
-                logits = loss_ce = loss_kd = loss = None  # noqa: F841
+                logits = loss_ce = loss_kd = loss = loss_pod = None  # noqa: F841
                 try:
                     graphed = _GraphedStep(step_fn, inputs, targets, model)
-                    logits, loss_ce, loss_kd, loss = graphed.out
+                    logits, loss_ce, loss_kd, loss, loss_pod = graphed.out
                 except Exception as e:
                     print(f"[engine] step-graph capture failed "
                           f"({type(e).__name__}: {e}); running eager")
                     can_graph = False
-                    logits, loss_ce, loss_kd, loss = step_fn(inputs, targets)
+                    logits, loss_ce, loss_kd, loss, loss_pod = step_fn(
+                        inputs, targets)
             elif graphed is not None:
-                logits, loss_ce, loss_kd, loss = graphed(inputs, targets)
+                logits, loss_ce, loss_kd, loss, loss_pod = graphed(
+                    inputs, targets)
             else:
-                logits, loss_ce, loss_kd, loss = step_fn(inputs, targets)
+                logits, loss_ce, loss_kd, loss, loss_pod = step_fn(
+                    inputs, targets)
                 if args.compat_step_barrier:
                     barrier()  # reference per-step barrier (template.py:272)
             first_of_epoch = False
@@ -271,6 +298,8 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                                     topk=(1, min(5, logits.shape[1])))
                 metric_logger.update(ce=loss_ce.item(), kd=loss_kd.item(),
                                      loss=loss.item())
+                if loss_pod is not None:
+                    metric_logger.update(pod=loss_pod.item())
                 metric_logger.update_n(n=bs, acc1=accs[0])
                 metric_logger.meters["lr"].update(optimizer.lr)
             step_i += 1

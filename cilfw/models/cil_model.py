@@ -90,7 +90,12 @@ class CilModel(nn.Module):
     def extract_vector(self, x):
         return self.backbone(x)
 
-    def forward(self, x):
+    def forward(self, x, return_maps=False):
+        """-> (logits, features); with ``return_maps`` -> (logits, features,
+        maps), maps = the backbone's stage outputs (for ops.pod_loss)."""
+        if return_maps:
+            features, maps = self.backbone(x, return_maps=True)
+            return self.fc(features), features, maps
         features = self.backbone(x)
         logits = self.fc(features)
         return logits, features

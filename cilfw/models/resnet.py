@@ -84,15 +84,20 @@ class ResNet(nn.Module):
         blocks += [block(self.in_ch, width, 1) for _ in range(n - 1)]
         return nn.Sequential(*blocks)
 
-    def forward(self, x):
+    def forward(self, x, return_maps=False):
+        """-> (N, out_dim) features; with ``return_maps`` also the list of
+        the four stage outputs (NHWC, post-ReLU)."""
         x = self.stem_bn(self.stem(x))
         if not self.small_input:
             x = CF.max_pool(x, 3, 2, 1)
-        x = self.layer1(x)
-        x = self.layer2(x)
-        x = self.layer3(x)
-        x = self.layer4(x)
-        return CF.global_avg_pool(x)
+        s1 = self.layer1(x)
+        s2 = self.layer2(s1)
+        s3 = self.layer3(s2)
+        s4 = self.layer4(s3)
+        feats = CF.global_avg_pool(s4)
+        if return_maps:
+            return feats, [s1, s2, s3, s4]
+        return feats
 
 
 def resnet18(small_input=True, **kw):

@@ -59,13 +59,17 @@ class CifarResNet(nn.Module):
         blocks += [BasicBlockA(out_ch, out_ch, 1) for _ in range(n - 1)]
         return nn.Sequential(*blocks)
 
-    def forward(self, x):
-        """x: (N,H,W,C) NHWC -> (N, out_dim) features."""
+    def forward(self, x, return_maps=False):
+        """x: (N,H,W,C) NHWC -> (N, out_dim) features; with ``return_maps``
+        also the list of the three stage outputs (NHWC, post-ReLU)."""
         x = self.bn_1(self.conv_1_3x3(x))
-        x = self.stage_1(x)
-        x = self.stage_2(x)
-        x = self.stage_3(x)
-        return CF.global_avg_pool(x)
+        s1 = self.stage_1(x)
+        s2 = self.stage_2(s1)
+        s3 = self.stage_3(s2)
+        feats = CF.global_avg_pool(s3)
+        if return_maps:
+            return feats, [s1, s2, s3]
+        return feats
 
 
 def resnet20(**kw):

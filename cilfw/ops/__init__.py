@@ -4,6 +4,7 @@ from .functional import (conv2d, batchnorm_act, batchnorm_add_relu, add_relu,
                          accuracy, max_pool, crop_resize,
                          crop_resize_ragged, crop_resize_ragged_reference)
 from .nme import nme_prototypes, nme_topk
+from .pod import pod_pool, pod_spatial, pod_dist, pod_loss
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
@@ -11,4 +12,5 @@ __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
            "global_avg_pool", "linear", "cross_entropy", "kd_loss", "wa_loss", "accuracy",
            "max_pool", "crop_resize", "crop_resize_ragged",
            "crop_resize_ragged_reference", "nme_prototypes", "nme_topk",
+           "pod_pool", "pod_spatial", "pod_dist", "pod_loss",
            "have_ext"]
