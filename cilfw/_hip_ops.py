@@ -548,6 +548,14 @@ def maxpool_bwd(dy, idx, H, W_, kernel, stride, pad):
 
 # ---------------------------------------------------------------------- linear
 
+def linear_ksplits(M, N, K):
+    """(fwd, dx, dW) split-K factors linear_fwd / linear_bwd launch with for
+    x (M, K), w (N, K): cilfw_linear_ksplit(rows, cols, reduce length)."""
+    return (_lib.cilfw_linear_ksplit(M, N, K),
+            _lib.cilfw_linear_ksplit(M, K, N),
+            _lib.cilfw_linear_ksplit(N, K, M))
+
+
 def linear_fwd(x, w, bias):
     _bf16(x, "linear.x")
     _bf16(w, "linear.w")
@@ -685,6 +693,10 @@ def sgd_step(p, g, m, lr_dev, momentum, wd, p_bf16=None):
 
 
 def topk_correct(logits, targets, maxk):
+    maxk = int(maxk)
+    if not 1 <= maxk <= 8:
+        # topk_kernel keeps the winners of earlier passes in excluded[8]
+        raise ValueError(f"topk_correct: maxk must be in 1..8 (got {maxk})")
     lf = logits.float().contiguous()
     M, C = lf.shape
     counts = torch.empty(maxk, dtype=torch.int64, device=lf.device)
