@@ -74,6 +74,11 @@ _PROTOS = {
     "cilfw_pod_pool": [c_vp] * 2 + [c_i] * 4 + [c_vp],
     "cilfw_pod_dist": [c_vp] * 5 + [c_i] * 2 + [c_vp],
     "cilfw_pod_bwd": [c_vp] * 4 + [c_i] * 4 + [c_vp],
+    "cilfw_rownorm_fwd": [c_vp] * 4 + [c_i] * 3 + [c_vp],
+    "cilfw_rownorm_bwd": [c_vp] * 6 + [c_i] * 3 + [c_vp],
+    "cilfw_cos_sum": [c_vp] * 2 + [c_i, c_f, c_vp],
+    "cilfw_flat_dist": [c_vp] * 5 + [c_i] * 2 + [c_vp],
+    "cilfw_flat_bwd": [c_vp] * 3 + [c_i] * 2 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -81,7 +86,9 @@ for _name, _args in _PROTOS.items():
     _fn.restype = None
 
 _lib.cilfw_conv2d_bwd_data.restype = c_i  # 1 = BN partials were emitted
-for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd"):
+for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd",
+              "cilfw_rownorm_fwd", "cilfw_rownorm_bwd", "cilfw_cos_sum",
+              "cilfw_flat_dist", "cilfw_flat_bwd"):
     getattr(_lib, _name).restype = c_i  # 1 = shape refused, nothing launched
 
 for _name, _n in [("cilfw_linear_ksplit", 3),
@@ -94,7 +101,8 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_bwd_data_route", 9),
                   ("cilfw_conv2d_bwd_weight_route", 8),
                   ("cilfw_pod_supported", 4),
-                  ("cilfw_pod_pool_groups", 2)]:
+                  ("cilfw_pod_pool_groups", 2),
+                  ("cilfw_cosine_supported", 3)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
@@ -979,4 +987,150 @@ def pod_bwd(a, gv, up, out=None):
                             c_i(H), c_i(W_), c_i(C), _stream())
     assert rc == 0, "pod_bwd: launcher refused the shape"
     _check("pod_bwd")
+    return out
+
+
+# ---------------------------------------------------------- cosine head / flat
+
+def _cos_rows(t, name, dtypes=(torch.bfloat16,)):
+    """(rows, D) matrix the row-normalisation kernels accept; the launchers
+    in csrc/cosine.hip apply the same rule (cilfw_cosine_supported)."""
+    assert t.dim() == 2, f"{name}: needs a (rows, D) matrix"
+    if dtypes == (torch.bfloat16,):
+        _bf16(t, name)
+    else:
+        assert t.dtype in dtypes, \
+            f"{name}: rows are bf16 or fp32 (got {t.dtype})"
+        assert t.is_contiguous(), f"{name}: needs contiguous tensor"
+    rows, D = t.shape
+    f32 = t.dtype == torch.float32
+    assert 1 <= D <= 2048, \
+        f"{name}: cosine kernels need 1 <= D <= 2048 (got D = {D})"
+    if f32:
+        assert D % 4 == 0, \
+            f"{name}: fp32 rows need D % 4 == 0 (got D = {D})"
+    else:
+        assert D % 8 == 0, \
+            f"{name}: bf16 rows need D % 8 == 0 (got D = {D})"
+    assert rows >= 1, f"{name}: needs rows >= 1"
+    assert _lib.cilfw_cosine_supported(rows, D, 1 if f32 else 0) == 1
+    assert t.data_ptr() % 16 == 0  # the kernels load 16-byte vectors
+    return rows, D, f32
+
+
+def _dev_scalar(s, ref, name):
+    if s is None:
+        return None
+    assert s.dtype == torch.float32 and s.numel() == 1 \
+        and s.device == ref.device, \
+        f"{name}: the scalar is a 1-element fp32 DEVICE tensor"
+    return s
+
+
+def rownorm_fwd(x, scale=None, out=None, rinv=None):
+    """x (rows, D) bf16 or fp32 -> (y bf16 (rows, D) = scale * x r(x), rinv
+    fp32 (rows,)), r(x) = 1/|x| or 0 for a zero row (csrc/cosine.hip).
+    ``scale``: 1-element fp32 DEVICE tensor read by the kernel (graph-safe) or
+    None for 1. ``out`` / ``rinv`` may be supplied (every element is
+    written)."""
+    rows, D, f32 = _cos_rows(x, "rownorm_fwd",
+                             (torch.bfloat16, torch.float32))
+    scale = _dev_scalar(scale, x, "rownorm_fwd")
+    if out is None:
+        out = torch.empty(rows, D, dtype=torch.bfloat16, device=x.device)
+    if rinv is None:
+        rinv = torch.empty(rows, dtype=torch.float32, device=x.device)
+    assert out.shape == (rows, D) and out.dtype == torch.bfloat16 \
+        and out.is_contiguous() and out.device == x.device \
+        and out.data_ptr() % 16 == 0
+    assert rinv.shape == (rows,) and rinv.dtype == torch.float32 \
+        and rinv.is_contiguous() and rinv.device == x.device
+    rc = _lib.cilfw_rownorm_fwd(_ptr(x), _ptr(scale), _ptr(out), _ptr(rinv),
+                                c_i(rows), c_i(D), c_i(1 if f32 else 0),
+                                _stream())
+    assert rc == 0, "rownorm_fwd: launcher refused the shape"
+    _check("rownorm_fwd")
+    return out, rinv
+
+
+def rownorm_bwd(x, rinv, g, scale=None, want_dsig=False, out=None):
+    """dx = (scale r) (g - x^ (x^ . g)), x^ = x r, in the dtype of x; g has
+    that dtype too (bf16 features, fp32 class weights). -> (dx, dsig fp32
+    (rows,) = x^ . g | None)."""
+    rows, D, f32 = _cos_rows(x, "rownorm_bwd",
+                             (torch.bfloat16, torch.float32))
+    assert g.shape == x.shape and g.dtype == x.dtype and g.is_contiguous() \
+        and g.device == x.device and g.data_ptr() % 16 == 0, \
+        "rownorm_bwd: the gradient has the shape and dtype of the rows"
+    assert rinv.shape == (rows,) and rinv.dtype == torch.float32 \
+        and rinv.is_contiguous() and rinv.device == x.device
+    scale = _dev_scalar(scale, x, "rownorm_bwd")
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype \
+        and out.is_contiguous() and out.device == x.device \
+        and out.data_ptr() % 16 == 0
+    dsig = (torch.empty(rows, dtype=torch.float32, device=x.device)
+            if want_dsig else None)
+    rc = _lib.cilfw_rownorm_bwd(_ptr(x), _ptr(rinv), _ptr(g), _ptr(scale),
+                                _ptr(out), _ptr(dsig), c_i(rows), c_i(D),
+                                c_i(1 if f32 else 0), _stream())
+    assert rc == 0, "rownorm_bwd: launcher refused the shape"
+    _check("rownorm_bwd")
+    return out, dsig
+
+
+def cos_sum(v, scale=1.0):
+    """scale * sum(v) of a 1-d fp32 tensor in a fixed order -> (1,) fp32."""
+    assert v.dim() == 1 and v.dtype == torch.float32 and v.is_contiguous() \
+        and 1 <= v.numel() < 2 ** 31
+    out = torch.empty(1, dtype=torch.float32, device=v.device)
+    rc = _lib.cilfw_cos_sum(_ptr(v), _ptr(out), c_i(v.numel()), c_f(scale),
+                            _stream())
+    assert rc == 0, "cos_sum: launcher refused the shape"
+    _check("cos_sum")
+    return out
+
+
+def flat_dist(s, t, out=None, rows_out=None):
+    """Student / teacher features (M, D) bf16 -> (loss 0-d fp32 = mean l, l
+    (M,) fp32 = |s^ - t^|^2 / 2, gs (M, D) fp32: d loss / d s for upstream
+    1)."""
+    M, D, _ = _cos_rows(s, "flat_dist.student")
+    assert t.shape == s.shape, \
+        f"flat_dist: student features {tuple(s.shape)} vs teacher " \
+        f"{tuple(t.shape)}"
+    _cos_rows(t, "flat_dist.teacher")
+    assert t.device == s.device
+    gs = out if out is not None else torch.empty(
+        M, D, dtype=torch.float32, device=s.device)
+    l = rows_out if rows_out is not None else torch.empty(
+        M, dtype=torch.float32, device=s.device)
+    assert gs.shape == (M, D) and gs.dtype == torch.float32 \
+        and gs.is_contiguous() and gs.data_ptr() % 16 == 0
+    assert l.shape == (M,) and l.dtype == torch.float32 and l.is_contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=s.device)
+    rc = _lib.cilfw_flat_dist(_ptr(s), _ptr(t), _ptr(gs), _ptr(l),
+                              _ptr(loss), c_i(M), c_i(D), _stream())
+    assert rc == 0, "flat_dist: launcher refused the shape"
+    _check("flat_dist")
+    return loss[0], l, gs
+
+
+def flat_bwd(gs, up, out=None):
+    """ds bf16 (M, D) = up * gs. ``up``: 1-element fp32 DEVICE tensor (read
+    by the kernel: no host sync, graph-safe)."""
+    M, D, _ = _cos_rows(gs, "flat_bwd", (torch.float32,))
+    assert D % 8 == 0, f"flat_bwd: bf16 rows need D % 8 == 0 (got D = {D})"
+    up = _dev_scalar(up, gs, "flat_bwd")
+    assert up is not None
+    if out is None:
+        out = torch.empty(M, D, dtype=torch.bfloat16, device=gs.device)
+    assert out.shape == (M, D) and out.dtype == torch.bfloat16 \
+        and out.is_contiguous() and out.device == gs.device \
+        and out.data_ptr() % 16 == 0
+    rc = _lib.cilfw_flat_bwd(_ptr(gs), _ptr(up), _ptr(out), c_i(M), c_i(D),
+                             _stream())
+    assert rc == 0, "flat_bwd: launcher refused the shape"
+    _check("flat_bwd")
     return out

@@ -41,6 +41,9 @@ def save_task_checkpoint(path_dir, task_id, model, memory, acc1s, args,
                 "python": random.getstate(),
             },
         }
+        if getattr(model, "head_kind", "linear") != "linear":
+            # optional key: absent means a linear head
+            state["head_kind"] = model.head_kind
         if getattr(args, "nme_eval", False):
             # optional key: absent from checkpoints written without the flag
             state["nme1s"] = list(getattr(args, "nme1s", []))
@@ -53,6 +56,12 @@ def load_task_checkpoint(path, model, memory, args, restore_rng=True):
     """Rebuild head structure, load weights/memory/counters. Returns the state
     dict (caller reads task_id / acc1s to continue the task loop)."""
     state = torch.load(path, map_location="cpu", weights_only=False)
+    saved_kind = state.get("head_kind", "linear")
+    model_kind = getattr(model, "head_kind", "linear")
+    if saved_kind != model_kind:
+        raise ValueError(
+            f"checkpoint {path} was written with --head {saved_kind}; this "
+            f"run uses --head {model_kind}")
     # grow the classifier to the checkpointed shape before loading weights
     for width in state["head_widths"]:
         model.prev_model_adaption(width)

@@ -80,6 +80,25 @@ def get_args_parser():
                              "paper (0 = off: no map is requested, no POD "
                              "kernel runs; combine with --lambda_kd 0 for "
                              "POD without logit KD)")
+    parser.add_argument("--lambda_flat", default=0.0, type=float,
+                        help="weight of the distillation of the final "
+                             "embedding against the frozen teacher, 1 - cos "
+                             "per sample (LUCIR's less-forget term, PODNet's "
+                             "POD-flat); scaled per task by "
+                             "sqrt(known_classes / increment) as in both "
+                             "papers (0 = off: no kernel of it runs; with "
+                             "--lambda_pod it completes PODNet's "
+                             "distillation)")
+    parser.add_argument("--head", default="linear",
+                        choices=["linear", "cosine"],
+                        help="classifier head: the growing linear head, "
+                             "bias-corrected after each task by weight "
+                             "aligning, or the cosine-normalised head of "
+                             "LUCIR / PODNet (logits = sigma * cos(feature, "
+                             "class weight); no bias, no weight aligning)")
+    parser.add_argument("--cos_scale_init", default=1.0, type=float,
+                        help="initial value of the cosine head's trained "
+                             "scale sigma (LUCIR starts at 1)")
 
     # ---- cilfw-native flags (no reference counterpart) ----
     parser.add_argument("--class_order", default=None, type=str,

@@ -195,31 +195,40 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
     if teacher is not None and getattr(args, "lambda_pod", 0.0) > 0:
         pod_w = args.lambda_pod * (known / args.increment_per_task) ** 0.5
     use_pod = pod_w > 0
+    # distillation of the final embedding (ops/cosine.py flat_loss), weighted
+    # like POD: lambda_flat * sqrt(known / increment). Off: the teacher's
+    # features are dropped as before and no kernel of the term is launched.
+    flat_w = 0.0
+    if teacher is not None and getattr(args, "lambda_flat", 0.0) > 0:
+        flat_w = args.lambda_flat * (known / args.increment_per_task) ** 0.5
+    use_flat = flat_w > 0
 
     def teacher_fwd(inputs):
-        """-> (t_logits, t_maps | None); the maps stay referenced until the
-        POD term has read them, like t_logits until wa_loss."""
+        """-> (t_logits, t_maps | None, t_features | None); the maps and the
+        features stay referenced until the POD / flat term has read them,
+        like t_logits until wa_loss."""
         if use_pod:
-            t_logits, _, t_maps = teacher(inputs, return_maps=True)
-            return t_logits, t_maps
-        return teacher(inputs)[0], None
+            t_logits, t_feat, t_maps = teacher(inputs, return_maps=True)
+            return t_logits, t_maps, (t_feat if use_flat else None)
+        t_logits, t_feat = teacher(inputs)
+        return t_logits, None, (t_feat if use_flat else None)
 
     def step_fn(inputs, targets, update=True):
         optimizer.zero_grad()
         if tstream is not None:
             tstream.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(tstream), torch.no_grad():
-                t_logits, t_maps = teacher_fwd(inputs)
+                t_logits, t_maps, t_features = teacher_fwd(inputs)
         if use_pod:
-            logits, _features, maps = model(inputs, return_maps=True)
+            logits, features, maps = model(inputs, return_maps=True)
         else:
-            logits, _features = model(inputs)
+            logits, features = model(inputs)
         if teacher is not None:
             if tstream is not None:
                 torch.cuda.current_stream().wait_stream(tstream)
             else:
                 with torch.no_grad():
-                    t_logits, t_maps = teacher_fwd(inputs)
+                    t_logits, t_maps, t_features = teacher_fwd(inputs)
             loss, loss_ce, loss_kd = ops.wa_loss(
                 logits, t_logits, targets, args.smooth,
                 args.kd_temperature, lambda_kd)
@@ -232,11 +241,16 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
             loss_pod = ops.pod_loss(maps, t_maps)
             loss = loss + pod_w * loss_pod
             loss_pod = loss_pod.detach()
+        loss_flat = None
+        if use_flat:
+            loss_flat = ops.flat_loss(features, t_features)
+            loss = loss + flat_w * loss_flat
+            loss_flat = loss_flat.detach()
         loss.backward()
         engine.finalize()
         if update:
             optimizer.step()
-        return logits, loss_ce, loss_kd, loss, loss_pod
+        return logits, loss_ce, loss_kd, loss, loss_pod, loss_flat
 
     import os as _os
     can_graph = (str(device).startswith("cuda") and not args.no_step_graph
@@ -273,21 +287,23 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                 # logits refs keep AccumulateGrad nodes pinned to the default
                 # stream, which breaks (segfaults) stream capture.
                 logits = loss_ce = loss_kd = loss = loss_pod = None  # noqa: F841
+                loss_flat = None  # noqa: F841
                 try:
                     graphed = _GraphedStep(step_fn, inputs, targets, model)
-                    logits, loss_ce, loss_kd, loss, loss_pod = graphed.out
+                    (logits, loss_ce, loss_kd, loss, loss_pod,
+                     loss_flat) = graphed.out
                 except Exception as e:
                     print(f"[engine] step-graph capture failed "
                           f"({type(e).__name__}: {e}); running eager")
                     can_graph = False
-                    logits, loss_ce, loss_kd, loss, loss_pod = step_fn(
-                        inputs, targets)
+                    (logits, loss_ce, loss_kd, loss, loss_pod,
+                     loss_flat) = step_fn(inputs, targets)
             elif graphed is not None:
-                logits, loss_ce, loss_kd, loss, loss_pod = graphed(
-                    inputs, targets)
+                (logits, loss_ce, loss_kd, loss, loss_pod,
+                 loss_flat) = graphed(inputs, targets)
             else:
-                logits, loss_ce, loss_kd, loss, loss_pod = step_fn(
-                    inputs, targets)
+                (logits, loss_ce, loss_kd, loss, loss_pod,
+                 loss_flat) = step_fn(inputs, targets)
                 if args.compat_step_barrier:
                     barrier()  # reference per-step barrier (template.py:272)
             first_of_epoch = False
@@ -300,6 +316,8 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                                      loss=loss.item())
                 if loss_pod is not None:
                     metric_logger.update(pod=loss_pod.item())
+                if loss_flat is not None:
+                    metric_logger.update(flat=loss_flat.item())
                 metric_logger.update_n(n=bs, acc1=accs[0])
                 metric_logger.meters["lr"].update(optimizer.lr)
             step_i += 1
@@ -387,7 +405,10 @@ def _run_tasks(args, device, watchdog):
     scenario_val, _ = build_dataset(is_train=False, args=args)
     args.nb_classes = nb_classes
 
-    model = CilModel(args.backbone, args.input_size).to(device)
+    model = CilModel(args.backbone, args.input_size,
+                     head=getattr(args, "head", "linear"),
+                     cos_scale_init=getattr(args, "cos_scale_init", 1.0)
+                     ).to(device)
     barrier()
 
     memory = RehearsalMemory(args.memory_size, args.herding_method,

@@ -10,6 +10,9 @@ Capability parity with reference template.py:87-166:
   after_model_adaption -> weight_align (:152-166).
 - weight_align: gamma = mean(||w_old rows||) / mean(||w_new rows||), rescales the
   NEWEST head's weight in place (the core WA step, template.py:156-166).
+- CosineClassifier (``CilModel(..., head="cosine")``): the cosine-normalised
+  head of LUCIR / PODNet, the other standard answer to the old-versus-new bias;
+  no reference counterpart.
 """
 
 import copy as _copy
@@ -18,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..ops import functional as CF
+from ..ops import cosine as COS
 from . import resnet_cifar, resnet
 
 
@@ -77,10 +81,60 @@ class CilClassifier(nn.Module):
         return len(self.heads)
 
 
-class CilModel(nn.Module):
-    def __init__(self, backbone_name, input_size=32):
+class CosineClassifier(nn.Module):
+    """Growable cosine-normalised classifier (LUCIR; PODNet's LSC head with
+    one proxy per class): logits = sigma * cos(feature, class weight), heads
+    concatenated in head order. No bias; ONE scale ``sigma`` shared by all
+    heads and trained like any other parameter. Rescaling a weight row cannot
+    change a logit, so no weight alignment applies."""
+
+    def __init__(self, embed_dim, nb_classes, scale_init=1.0):
         super().__init__()
+        self.embed_dim = embed_dim
+        self.heads = nn.ModuleList()
+        self.sigma = nn.Parameter(torch.full((1,), float(scale_init)))
+        self.adaption(nb_classes)
+
+    def adaption(self, nb_new_classes):
+        head = nn.Module()
+        head.weight = nn.Parameter(torch.empty(nb_new_classes, self.embed_dim))
+        nn.init.kaiming_normal_(head.weight)
+        head.out_features = nb_new_classes
+        self.heads.append(head)
+
+    @property
+    def nb_classes(self):
+        return sum(h.out_features for h in self.heads)
+
+    def forward(self, x):
+        # one cosine_linear over the row-concatenated fp32 masters; a frozen
+        # model uses its cached normalised rows (cast_compute_weights_)
+        cat = getattr(self, "_frozen_cat", None)
+        if cat is not None:
+            return COS.cosine_linear_frozen(x, cat[0], cat[1])
+        w = torch.cat([h.weight for h in self.heads], dim=0)
+        return COS.cosine_linear(x, w, self.sigma)
+
+    def __getitem__(self, i):
+        return self.heads[i]
+
+    def __len__(self):
+        return len(self.heads)
+
+
+HEAD_KINDS = ("linear", "cosine")
+
+
+class CilModel(nn.Module):
+    def __init__(self, backbone_name, input_size=32, head="linear",
+                 cos_scale_init=1.0):
+        super().__init__()
+        if head not in HEAD_KINDS:
+            raise ValueError(f"unknown head kind {head!r} (one of "
+                             f"{HEAD_KINDS})")
         self.backbone = get_backbone(backbone_name, input_size)
+        self.head_kind = head
+        self.cos_scale_init = cos_scale_init
         self.fc = None
 
     @property
@@ -140,7 +194,15 @@ class CilModel(nn.Module):
                 invstd = torch.rsqrt(m.running_var.float() + m.eps)
                 m.running_mean._cilfw_frozen = (mean.contiguous(),
                                                 invstd.contiguous())
-        if self.fc is not None:
+        if isinstance(self.fc, CosineClassifier):
+            # the normalisation reads the fp32 masters, which stay as they
+            # are; the unit rows (the GEMM operand) and sigma are cached once,
+            # so a frozen head costs one rownorm_fwd on the features + the GEMM
+            w = torch.cat([h.weight for h in self.fc.heads], 0).float()
+            self.fc._frozen_cat = (
+                COS.cosine_normalize_weights(w).to(dtype).contiguous(),
+                self.fc.sigma.detach().float().clone())
+        elif self.fc is not None:
             for h in self.fc.heads:
                 h.weight.data = h.weight.data.to(dtype)
                 h.bias.data = h.bias.data.to(dtype)
@@ -151,7 +213,11 @@ class CilModel(nn.Module):
 
     def prev_model_adaption(self, nb_classes):
         if self.fc is None:
-            self.fc = CilClassifier(self.feature_dim, nb_classes)
+            if self.head_kind == "cosine":
+                self.fc = CosineClassifier(self.feature_dim, nb_classes,
+                                           self.cos_scale_init)
+            else:
+                self.fc = CilClassifier(self.feature_dim, nb_classes)
         else:
             self.fc.adaption(nb_classes)
         # keep the new head on the model's device/dtype
@@ -162,11 +228,19 @@ class CilModel(nn.Module):
         task_id = getattr(args, "task_id", len(self.fc) - 1) if args is not None \
             else len(self.fc) - 1
         if task_id > 0:
+            if self.head_kind == "cosine":
+                print("cosine head: weight aligning skipped (rescaling a "
+                      "weight row cannot change a cosine logit)")
+                return
             self.weight_align(nb_classes)
 
     @torch.no_grad()
     def weight_align(self, nb_new_classes):
         """WA: rescale the newest head so mean new-row norm == mean old-row norm."""
+        if self.head_kind == "cosine":
+            raise RuntimeError(
+                "weight_align: a cosine head has no row norms to align "
+                "(its logits are invariant under rescaling a weight row)")
         w = torch.cat([h.weight for h in self.fc.heads], dim=0)
         norms = torch.norm(w, p=2, dim=1)
         norm_old = norms[:-nb_new_classes]

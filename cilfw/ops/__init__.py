@@ -5,6 +5,7 @@ from .functional import (conv2d, batchnorm_act, batchnorm_add_relu, add_relu,
                          crop_resize_ragged, crop_resize_ragged_reference)
 from .nme import nme_prototypes, nme_topk
 from .pod import pod_pool, pod_spatial, pod_dist, pod_loss
+from .cosine import cosine_linear, flat_loss, flat_dist
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
@@ -13,4 +14,5 @@ __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
            "max_pool", "crop_resize", "crop_resize_ragged",
            "crop_resize_ragged_reference", "nme_prototypes", "nme_topk",
            "pod_pool", "pod_spatial", "pod_dist", "pod_loss",
+           "cosine_linear", "flat_loss", "flat_dist",
            "have_ext"]
