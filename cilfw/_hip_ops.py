@@ -36,7 +36,7 @@ _lib.cilfw_error_string.argtypes = [c_i]
 _PROTOS = {
     "cilfw_conv2d_fwd": [c_vp] * 4 + [c_i] * 12 + [c_vp, c_vp],
     "cilfw_conv2d_bwd_data": [c_vp] * 4 + [c_i] * 12 + [c_vp] * 5 + [c_i, c_vp],
-    "cilfw_conv2d_bwd_weight": [c_vp] * 5 + [c_i] * 13 + [c_vp],
+    "cilfw_conv2d_bwd_weight": [c_vp] * 4 + [c_i] * 13 + [c_vp],
     "cilfw_fill_mtable": [c_vp] + [c_i] * 4 + [c_vp],
     "cilfw_im2col_smallc": [c_vp] * 3 + [c_i] * 11 + [c_vp],
     "cilfw_bn_apply_only": [c_vp] * 7 + [c_l, c_i, c_i, c_vp],
@@ -48,8 +48,6 @@ _PROTOS = {
     "cilfw_downsample_a_bwd": [c_vp] * 2 + [c_i] * 4 + [c_vp],
     "cilfw_gap_fwd": [c_vp] * 2 + [c_i] * 3 + [c_vp],
     "cilfw_gap_bwd": [c_vp] * 2 + [c_i] * 3 + [c_vp],
-    "cilfw_conv2d_bwd_data_sub": [c_vp] * 4 + [c_i] * 12 + [c_vp],
-    "cilfw_parity_scatter": [c_vp] * 2 + [c_i] * 8 + [c_vp],
     "cilfw_stride_gather": [c_vp] * 2 + [c_i] * 7 + [c_vp],
     "cilfw_stride_scatter": [c_vp] * 2 + [c_i] * 7 + [c_vp],
     "cilfw_maxpool_fwd": [c_vp] * 3 + [c_i] * 9 + [c_vp],
@@ -96,6 +94,8 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_bwd_data_ksplit", 7),
                   ("cilfw_conv2d_bwd_data_can_fuse_bn", 8),
                   ("cilfw_conv2d_bwd_data_bn_gy", 3),
+                  ("cilfw_conv2d_fwd_bn_gy", 3),
+                  ("cilfw_bnbwd_fuse_enabled", 0),
                   ("cilfw_conv2d_bwd_weight_nslices", 7),
                   ("cilfw_conv2d_fwd_route", 8),
                   ("cilfw_conv2d_bwd_data_route", 9),
@@ -106,6 +106,8 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
+_lib.cilfw_bn_sums_gy.argtypes = [c_l]
+_lib.cilfw_bn_sums_gy.restype = c_i
 
 # route codes of csrc/conv.hip (enum order); the launchers branch on the same
 # C functions these queries call
@@ -141,27 +143,44 @@ def _bf16(t, name):
 
 # ------------------------------------------------------------------------ conv
 
-def _stem_cols(x, stride, pad, R, S, CRSpad):
-    """Padded im2col for tiny-C stems -> (M, CRSpad) bf16 (pre-zeroed)."""
+def _out_hw(H, W_, R, S, stride, pad):
+    return ((H + 2 * pad - R) // stride + 1,
+            (W_ + 2 * pad - S) // stride + 1)
+
+
+def _crs_pad(C, R, S):
+    """C*R*S rounded up to the 16-element k-chunks of the fast GEMM path:
+    row length of the padded stem im2col."""
+    return (C * R * S + 15) // 16 * 16
+
+
+def _slab_ws(nslabs, numel, device, always=False):
+    """fp32 split-K workspace [nslabs][numel]; None when a single slice
+    stores its result directly (bwd-weight ``always`` goes through slabs)."""
+    if nslabs > 1 or always:
+        return torch.empty(nslabs * numel, dtype=torch.float32, device=device)
+    return None
+
+
+def _stem_as_1x1(x, R, S, stride, pad, Ho, Wo):
+    """Padded im2col for tiny-C stems: x as the (M, 1, 1, CRSpad) bf16 input
+    of a 1x1 conv (pad columns zero)."""
     N, H, W_, C = x.shape
-    Ho = (H + 2 * pad - R) // stride + 1
-    Wo = (W_ + 2 * pad - S) // stride + 1
-    M = N * Ho * Wo
+    M, CRSpad = N * Ho * Wo, _crs_pad(C, R, S)
     mt = _mtable(N, Ho, Wo, stride, x.device)
-    col = torch.zeros(M, CRSpad, dtype=torch.bfloat16, device=x.device)
+    col = torch.zeros(M, 1, 1, CRSpad, dtype=torch.bfloat16, device=x.device)
     _lib.cilfw_im2col_smallc(_ptr(x), _ptr(mt), _ptr(col), c_i(N), c_i(H),
                              c_i(W_), c_i(C), c_i(R), c_i(S), c_i(stride),
                              c_i(pad), c_i(Ho), c_i(Wo), c_i(CRSpad),
                              _stream())
     _check("im2col_smallc")
-    return col, Ho, Wo
+    return col
 
 
 def conv2d_fwd_route(N, H, W_, C, K, R, S, stride, pad):
     """(route name, ksplit) conv2d_fwd takes for this geometry outside graph
     capture: v1_bk32 | v1_bk64 | v2_bn64 | v2_bn128."""
-    Ho = (H + 2 * pad - R) // stride + 1
-    Wo = (W_ + 2 * pad - S) // stride + 1
+    Ho, Wo = _out_hw(H, W_, R, S, stride, pad)
     ks = _lib.cilfw_conv2d_fwd_ksplit(N, C, K, R, S, Ho, Wo)
     return _FWD_ROUTES[_lib.cilfw_conv2d_fwd_route(N, C, K, R, S, Ho, Wo,
                                                    ks)], ks
@@ -176,6 +195,11 @@ def conv2d_bwd_data_route(N, H, W_, C, K, R, S, stride):
     ks = _lib.cilfw_conv2d_bwd_data_ksplit(N, H, W_, C, K, R, S)
     return _BWD_DATA_ROUTES[_lib.cilfw_conv2d_bwd_data_route(
         N, H, W_, C, K, R, S, stride, ks)], ks
+
+
+def bnbwd_fuse_enabled():
+    """CILFW_BNBWD_FUSE, as csrc/conv.hip (the knob's one reader) sees it."""
+    return bool(_lib.cilfw_bnbwd_fuse_enabled())
 
 
 def _stem_im2col_dw(C, K, R, S):
@@ -193,8 +217,7 @@ def conv2d_bwd_weight_route(N, C, K, R, S, Ho, Wo, accum=False):
     v1_generic. Tiny-C stems on the im2col route run the flat GEMM over the
     padded (M, CRSpad) columns, which never accumulates in-kernel."""
     if _stem_im2col_dw(C, K, R, S):
-        N, C, R, S, Ho, Wo = N * Ho * Wo, (C * R * S + 15) // 16 * 16, 1, 1, \
-            1, 1
+        N, C, R, S, Ho, Wo = N * Ho * Wo, _crs_pad(C, R, S), 1, 1, 1, 1
         accum = False
     ns = _lib.cilfw_conv2d_bwd_weight_nslices(N, C, K, R, S, Ho, Wo)
     return _BWD_WEIGHT_ROUTES[_lib.cilfw_conv2d_bwd_weight_route(
@@ -204,49 +227,37 @@ def conv2d_bwd_weight_route(N, C, K, R, S, Ho, Wo, accum=False):
 def conv2d_fwd(x, w, stride, pad, want_bn_parts=False):
     """want_bn_parts: also produce per-M-block per-channel (sum, sumsq)
     partials of y in the conv epilogue — a following training-mode BN skips
-    its own bn_sums pass (and a full re-read of y). Returns (y, parts|None);
-    parts is None when the shape routed off the v2 kernel or used split-K."""
+    its own bn_sums pass (and a full re-read of y). Returns (y, parts|None):
+    parts is (gy, 2, K) fp32, None when the shape routed off the v2 kernel or used split-K."""
     _bf16(x, "conv2d_fwd.x")
     _bf16(w, "conv2d_fwd.w")
     N, H, W_, C = x.shape
     R, S, Cw, K = w.shape
     assert Cw == C
     assert K % 8 == 0, "conv kernels vector-stage over output channels (K%8==0)"
-    Ho = (H + 2 * pad - R) // stride + 1
-    Wo = (W_ + 2 * pad - S) // stride + 1
+    Ho, Wo = _out_hw(H, W_, R, S, stride, pad)
     if C < 16 and R * S > 1 and K % 16 == 0 \
             and os.environ.get("CILFW_STEM_IM2COL") == "1":
         # measured: the generic gather already fills the chip at stem sizes —
-        # this alternate path is kept for experiments (CILFW_STEM_IM2COL=1)
-        CRS = C * R * S
-        CRSpad = (CRS + 15) // 16 * 16
-        col, Ho, Wo = _stem_cols(x, stride, pad, R, S, CRSpad)
-        M = N * Ho * Wo
-        wpad = torch.zeros(CRSpad, K, dtype=torch.bfloat16, device=x.device)
-        wpad[:CRS] = w.reshape(CRS, K)
-        y = torch.empty(M, K, dtype=torch.bfloat16, device=x.device)
-        ks = _lib.cilfw_conv2d_fwd_ksplit(M, CRSpad, K, 1, 1, 1, 1)
-        ws = (torch.empty(ks * M * K, dtype=torch.float32, device=x.device)
-              if ks > 1 else None)
-        _lib.cilfw_conv2d_fwd(_ptr(col), _ptr(wpad), _ptr(y), _ptr(ws),
-                              c_i(M), c_i(1), c_i(1), c_i(CRSpad), c_i(K),
-                              c_i(1), c_i(1), c_i(1), c_i(0), c_i(1), c_i(1),
-                              c_i(ks), _ptr(None), _stream())
-        _check("conv2d_fwd_stem")
+        # this alternate path is kept for experiments (CILFW_STEM_IM2COL=1):
+        # a 1x1 conv over the padded im2col columns
+        col = _stem_as_1x1(x, R, S, stride, pad, Ho, Wo)
+        wpad = torch.zeros(1, 1, col.shape[-1], K, dtype=torch.bfloat16,
+                           device=x.device)
+        wpad[0, 0, :C * R * S] = w.reshape(C * R * S, K)
+        y, _ = conv2d_fwd(col, wpad, 1, 0)
         return y.view(N, Ho, Wo, K), None
     y = torch.empty(N, Ho, Wo, K, dtype=torch.bfloat16, device=x.device)
     ks = _lib.cilfw_conv2d_fwd_ksplit(N, C, K, R, S, Ho, Wo)
-    ws = (torch.empty(ks * N * Ho * Wo * K, dtype=torch.float32,
-                      device=x.device) if ks > 1 else None)
+    ws = _slab_ws(ks, y.numel(), x.device)
     parts = None
     # the BN-statistics epilogue lives in the v2 kernels' ksplit==1 stores
     if want_bn_parts and ks == 1 \
             and _FWD_ROUTES[_lib.cilfw_conv2d_fwd_route(
                 N, C, K, R, S, Ho, Wo, ks)].startswith("v2_") \
             and os.environ.get("CILFW_CONV_BN_FUSE", "1") != "0":
-        gy = (N * Ho * Wo + 127) // 128
-        parts = torch.empty(gy * 2 * K, dtype=torch.float32,
-                            device=x.device)
+        parts = torch.empty(_lib.cilfw_conv2d_fwd_bn_gy(N, Ho, Wo), 2, K,
+                            dtype=torch.float32, device=x.device)
     _lib.cilfw_conv2d_fwd(_ptr(x), _ptr(w), _ptr(y), _ptr(ws), c_i(N),
                           c_i(H), c_i(W_), c_i(C), c_i(K), c_i(R), c_i(S),
                           c_i(stride), c_i(pad), c_i(Ho), c_i(Wo), c_i(ks),
@@ -277,38 +288,25 @@ def conv2d_bwd_data(dy, w, stride, pad, H, W_, bn_meta=None):
         # keep the return shape contract: callers that passed bn_meta unpack
         # a (dx, parts) pair (no fusion on the strided-1x1 scatter path)
         return (dx, None) if bn_meta is not None else dx
-    # NOTE: a 4-way parity decomposition of stride-2 bwd-data was measured
-    # SLOWER than the single zero-structured kernel (12 small launches vs one
-    # big one) — kernels kept (cilfw_conv2d_bwd_data_sub/parity_scatter) for a
-    # future fused single-launch variant.
     dx = torch.empty(N, H, W_, C, dtype=torch.bfloat16, device=dy.device)
     ks = _lib.cilfw_conv2d_bwd_data_ksplit(N, H, W_, C, K, R, S)
-    ws = (torch.empty(ks * N * H * W_ * C, dtype=torch.float32,
-                      device=dy.device) if ks > 1 else None)
+    ws = _slab_ws(ks, dx.numel(), dy.device)
     parts = None
+    bn_y = bn_x = bn_mean = bn_invstd = None  # null pointers: nothing fused
+    bn_relu = False
     if (bn_meta is not None
             and _lib.cilfw_conv2d_bwd_data_can_fuse_bn(
                 N, H, W_, C, K, R, S, stride)):
-        gy = _lib.cilfw_conv2d_bwd_data_bn_gy(N, H, W_)
-        parts = torch.empty(gy, 2, C, dtype=torch.float32, device=dy.device)
-    if parts is not None:
         bn_y, bn_x, bn_mean, bn_invstd, bn_relu = bn_meta
-        fused = _lib.cilfw_conv2d_bwd_data(
-            _ptr(dy), _ptr(w), _ptr(dx), _ptr(ws), c_i(N),
-            c_i(H), c_i(W_), c_i(C), c_i(K), c_i(R),
-            c_i(S), c_i(stride), c_i(pad), c_i(Ho),
-            c_i(Wo), c_i(ks), _ptr(bn_y), _ptr(bn_x), _ptr(bn_mean),
-            _ptr(bn_invstd), _ptr(parts), c_i(1 if bn_relu else 0),
-            _stream())
-        if not fused:
-            parts = None
-    else:
-        _lib.cilfw_conv2d_bwd_data(
-            _ptr(dy), _ptr(w), _ptr(dx), _ptr(ws), c_i(N),
-            c_i(H), c_i(W_), c_i(C), c_i(K), c_i(R),
-            c_i(S), c_i(stride), c_i(pad), c_i(Ho),
-            c_i(Wo), c_i(ks), c_vp(0), c_vp(0), c_vp(0), c_vp(0), c_vp(0),
-            c_i(0), _stream())
+        parts = torch.empty(_lib.cilfw_conv2d_bwd_data_bn_gy(N, H, W_), 2, C,
+                            dtype=torch.float32, device=dy.device)
+    fused = _lib.cilfw_conv2d_bwd_data(
+        _ptr(dy), _ptr(w), _ptr(dx), _ptr(ws), c_i(N), c_i(H), c_i(W_),
+        c_i(C), c_i(K), c_i(R), c_i(S), c_i(stride), c_i(pad), c_i(Ho),
+        c_i(Wo), c_i(ks), _ptr(bn_y), _ptr(bn_x), _ptr(bn_mean),
+        _ptr(bn_invstd), _ptr(parts), c_i(1 if bn_relu else 0), _stream())
+    if not fused:
+        parts = None
     _check("conv2d_bwd_data")
     if bn_meta is not None:
         return dx, parts
@@ -343,22 +341,10 @@ def conv2d_bwd_weight(dy, x, stride, pad, R, S, out=None, accum=False):
     N, H, W_, C = x.shape
     _, Ho, Wo, K = dy.shape
     if _stem_im2col_dw(C, K, R, S):
-        CRS = C * R * S
-        CRSpad = (CRS + 15) // 16 * 16
-        col, _, _ = _stem_cols(x, stride, pad, R, S, CRSpad)
-        M = N * Ho * Wo
-        dyf = dy.reshape(M, K)
-        dwp = torch.empty(CRSpad, K, dtype=torch.float32, device=x.device)
-        ns = _lib.cilfw_conv2d_bwd_weight_nslices(M, CRSpad, K, 1, 1, 1, 1)
-        ws = torch.empty(ns * CRSpad * K, dtype=torch.float32,
-                         device=x.device)
-        _lib.cilfw_conv2d_bwd_weight(_ptr(dyf), _ptr(col), _ptr(None),
-                                     _ptr(dwp), _ptr(ws), c_i(M), c_i(1),
-                                     c_i(1), c_i(CRSpad), c_i(K), c_i(1),
-                                     c_i(1), c_i(1), c_i(0), c_i(1), c_i(1),
-                                     c_i(ns), c_i(0), _stream())
-        _check("conv2d_bwd_weight_stem")
-        dw = dwp[:CRS].reshape(R, S, C, K)
+        # dW of the 1x1 conv over the padded im2col columns; pad rows dropped
+        col = _stem_as_1x1(x, R, S, stride, pad, Ho, Wo)
+        dwp = conv2d_bwd_weight(dy.view(-1, 1, 1, K), col, 1, 0, 1, 1)
+        dw = dwp.view(-1, K)[:C * R * S].reshape(R, S, C, K)
         if out is None:
             return dw
         (out.add_(dw) if accum else out.copy_(dw))
@@ -370,7 +356,6 @@ def conv2d_bwd_weight(dy, x, stride, pad, R, S, out=None, accum=False):
                                  _stream())
         _check("stride_gather")
         return conv2d_bwd_weight(dy, xg, 1, 0, R, S, out=out, accum=accum)
-    mt = _mtable(N, Ho, Wo, stride, dy.device)
     if out is None:
         dw = torch.empty(R, S, C, K, dtype=torch.float32, device=dy.device)
         accum = False
@@ -379,9 +364,8 @@ def conv2d_bwd_weight(dy, x, stride, pad, R, S, out=None, accum=False):
             and out.shape == (R, S, C, K)
         dw = out
     ns = _lib.cilfw_conv2d_bwd_weight_nslices(N, C, K, R, S, Ho, Wo)
-    ws = torch.empty(ns * R * S * C * K, dtype=torch.float32,
-                     device=dy.device)
-    _lib.cilfw_conv2d_bwd_weight(_ptr(dy), _ptr(x), _ptr(mt), _ptr(dw),
+    ws = _slab_ws(ns, dw.numel(), dy.device, always=True)
+    _lib.cilfw_conv2d_bwd_weight(_ptr(dy), _ptr(x), _ptr(dw),
                                  _ptr(ws), c_i(N), c_i(H), c_i(W_), c_i(C),
                                  c_i(K), c_i(R), c_i(S), c_i(stride),
                                  c_i(pad), c_i(Ho), c_i(Wo), c_i(ns),
@@ -393,8 +377,8 @@ def conv2d_bwd_weight(dy, x, stride, pad, R, S, out=None, accum=False):
 # -------------------------------------------------------------------------- bn
 
 def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, training,
-           relu, residual=None, ext_parts=None, ext_gy=0):
-    """ext_parts/ext_gy: per-M-block (sum, sumsq) partials produced by the
+           relu, residual=None, ext_parts=None):
+    """ext_parts: (gy, 2, C) per-M-block (sum, sumsq) partials produced by the
     conv that made x (conv2d_fwd want_bn_parts) — skips the bn_sums pass."""
     _bf16(x, "bn_fwd.x")
     if residual is not None:
@@ -420,13 +404,14 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, training,
     y = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    gy = (M + 255) // 256  # keep in sync with rows_per_blk=256 in norm.hip
+    gy = _lib.cilfw_bn_sums_gy(M)
     scratch = torch.empty((gy + 1) * 2 * C, dtype=torch.float32,
                           device=x.device)
     gf = gamma.float().contiguous()
     bf = beta.float().contiguous()
     if not training:
         ext_parts = None
+    ext_gy = 0 if ext_parts is None else ext_parts.shape[0]
     _lib.cilfw_bn_fwd(_ptr(x), _ptr(y), _ptr(residual), _ptr(gf), _ptr(bf),
                       _ptr(running_mean), _ptr(running_var), _ptr(mean),
                       _ptr(invstd), _ptr(scratch), _ptr(ext_parts),
@@ -455,7 +440,7 @@ def bn_bwd(dy, x, gamma, mean, invstd, y, relu, training, want_dres=False,
         base = 0
     else:
         ext_gy = 0
-        gy = (M + 255) // 256  # keep in sync with rows_per_blk in norm.hip
+        gy = _lib.cilfw_bn_sums_gy(M)
         dgb = torch.empty((gy + 1) * 2 * C, dtype=torch.float32,
                           device=x.device)
         base = gy * 2 * C
@@ -718,17 +703,12 @@ def topk_correct(logits, targets, maxk):
 _CROP_RESIZE_MODES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}
 
 
-def crop_resize(src, idx, params, flip, out_size, mean255, std255, dtype):
-    """Fused gather -> affine bilinear resample -> flip -> quantize ->
-    normalize (csrc/data.hip). src uint8 (M,Hs,Ws,C); idx int64 (N,) or None;
-    params fp32 (N,4) = (oy, ox, sy, sx); flip uint8 (N,). mean255/std255
-    None -> uint8 levels, else normalized ``dtype`` (fp32 / bf16)."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.is_contiguous()
-    M, Hs, Ws, C = src.shape
-    S = int(out_size)
-    assert 1 <= C <= 4 and M >= 1 and Hs >= 1 and Ws >= 1 and S >= 1
-    assert S * S * C < 2 ** 31 and Hs * Ws * C < 2 ** 31
-    dev = src.device
+def _crop_args(name, dev, M, C, S, idx, params, flip, mean255, std255, dtype,
+               move_stats):
+    """Validation shared by crop_resize / crop_resize_ragged -> (N, idx,
+    params, flip, mean255, std255, out). idx None samples all M sources.
+    move_stats: mean255/std255 are moved to ``dev``; otherwise they must
+    already live there."""
     if idx is not None:
         assert idx.dtype == torch.int64 and idx.dim() == 1 \
             and idx.device == dev
@@ -747,16 +727,35 @@ def crop_resize(src, idx, params, flip, out_size, mean255, std255, dtype):
         dtype = torch.uint8
     else:
         assert dtype in (torch.float32, torch.bfloat16), \
-            f"crop_resize: normalized output is fp32 or bf16 (got {dtype})"
-        mean255 = mean255.to(dev, torch.float32).reshape(-1).contiguous()
-        std255 = std255.to(dev, torch.float32).reshape(-1).contiguous()
+            f"{name}: normalized output is fp32 or bf16 (got {dtype})"
+        if move_stats:
+            mean255, std255 = mean255.to(dev), std255.to(dev)
+        assert mean255.device == dev and std255.device == dev
+        mean255 = mean255.to(torch.float32).reshape(-1).contiguous()
+        std255 = std255.to(torch.float32).reshape(-1).contiguous()
         assert mean255.numel() == C and std255.numel() == C
     out = torch.empty(N, S, S, C, dtype=dtype, device=dev)
     assert out.data_ptr() % 16 == 0  # the kernel stores 16-byte vectors
+    return N, idx, params, flip, mean255, std255, out
+
+
+def crop_resize(src, idx, params, flip, out_size, mean255, std255, dtype):
+    """Fused gather -> affine bilinear resample -> flip -> quantize ->
+    normalize (csrc/data.hip). src uint8 (M,Hs,Ws,C); idx int64 (N,) or None;
+    params fp32 (N,4) = (oy, ox, sy, sx); flip uint8 (N,). mean255/std255
+    None -> uint8 levels, else normalized ``dtype`` (fp32 / bf16)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.is_contiguous()
+    M, Hs, Ws, C = src.shape
+    S = int(out_size)
+    assert 1 <= C <= 4 and M >= 1 and Hs >= 1 and Ws >= 1 and S >= 1
+    assert S * S * C < 2 ** 31 and Hs * Ws * C < 2 ** 31
+    N, idx, params, flip, mean255, std255, out = _crop_args(
+        "crop_resize", src.device, M, C, S, idx, params, flip, mean255,
+        std255, dtype, move_stats=True)
     _lib.cilfw_crop_resize(_ptr(src), _ptr(idx), _ptr(params), _ptr(flip),
                            _ptr(mean255), _ptr(std255), _ptr(out), c_i(M),
                            c_i(N), c_i(Hs), c_i(Ws), c_i(C), c_i(S),
-                           c_i(_CROP_RESIZE_MODES[dtype]), _stream())
+                           c_i(_CROP_RESIZE_MODES[out.dtype]), _stream())
     _check("crop_resize")
     return out
 
@@ -780,33 +779,14 @@ def crop_resize_ragged(pool, offsets, hw, channels, idx, params, flip,
         and hw.device == dev and hw.is_contiguous()
     assert 1 <= C <= 4 and M >= 1 and S >= 1
     assert S * S * C < 2 ** 31
-    assert idx is not None and idx.dtype == torch.int64 and idx.dim() == 1 \
-        and idx.device == dev
-    idx = idx.contiguous()
-    N = idx.shape[0]
-    assert params.shape == (N, 4) and params.dtype == torch.float32 \
-        and params.device == dev
-    assert flip.shape == (N,) and flip.dtype == torch.uint8 \
-        and flip.device == dev
-    params = params.contiguous()
-    flip = flip.contiguous()
-    if mean255 is None:
-        assert std255 is None
-        dtype = torch.uint8
-    else:
-        assert dtype in (torch.float32, torch.bfloat16), \
-            f"crop_resize_ragged: normalized output is fp32 or bf16 " \
-            f"(got {dtype})"
-        assert mean255.device == dev and std255.device == dev
-        mean255 = mean255.to(torch.float32).reshape(-1).contiguous()
-        std255 = std255.to(torch.float32).reshape(-1).contiguous()
-        assert mean255.numel() == C and std255.numel() == C
-    out = torch.empty(N, S, S, C, dtype=dtype, device=dev)
-    assert out.data_ptr() % 16 == 0  # the kernel stores 16-byte vectors
+    assert idx is not None
+    N, idx, params, flip, mean255, std255, out = _crop_args(
+        "crop_resize_ragged", dev, M, C, S, idx, params, flip, mean255,
+        std255, dtype, move_stats=False)
     _lib.cilfw_crop_resize_ragged(
         _ptr(pool), _ptr(offsets), _ptr(hw), _ptr(idx), _ptr(params),
         _ptr(flip), _ptr(mean255), _ptr(std255), _ptr(out), c_i(M), c_i(N),
-        c_i(C), c_i(S), c_i(_CROP_RESIZE_MODES[dtype]), _stream())
+        c_i(C), c_i(S), c_i(_CROP_RESIZE_MODES[out.dtype]), _stream())
     _check("crop_resize_ragged")
     return out
 

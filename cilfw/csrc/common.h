@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define WAVE 64
 #define DEV __device__ __forceinline__
@@ -28,6 +29,14 @@ DEV bf16_t f2bf(float f) {
 
 DEV int cdiv_i(int a, int b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Integer environment knob (unset -> dflt). Cache it at the call site:
+//   static const int v = env_int("CILFW_X", 512);
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline int env_set(const char* name) { return getenv(name) != nullptr; }
 
 // ---- MFMA 16x16x32 bf16 fragment maps (verified by tests/test_ops_gpu.py) ----
 // A (16x32):  row i = lane & 15, k = (lane >> 4) * 8 + j   (j = 0..7)

@@ -109,8 +109,7 @@ __global__ __launch_bounds__(NTHREADS)
 void conv2d_fwd_kernel(const bf16_t* __restrict__ x,
                        const bf16_t* __restrict__ w,
                        bf16_t* __restrict__ y, float* __restrict__ ws,
-                       ConvGeom g, int M, int CRS, int nk, int fast_a,
-                       int ksplit) {
+                       ConvGeom g, int M, int CRS, int nk, int ksplit) {
   constexpr int NQ = BKT / 32;      // 16-elem chunks per thread in A staging
   constexpr int LPX = BKT + 8;
   constexpr int NR = BMX / 128;     // A-tile rows per thread (1 or 2)
@@ -321,8 +320,7 @@ __global__ __launch_bounds__(NTHREADS)
 void conv2d_bwd_data_kernel(const bf16_t* __restrict__ dy,
                             const bf16_t* __restrict__ w,
                             bf16_t* __restrict__ dx, float* __restrict__ ws,
-                            ConvGeom g, int M, int RSK, int nk, int fast_a,
-                            int ksplit,
+                            ConvGeom g, int M, int RSK, int nk, int ksplit,
                             // BNP epilogue: per-block (dgamma, dbeta)
                             // partials of the downstream training BN whose
                             // backward consumes this dx as its dy (the BN's
@@ -782,7 +780,7 @@ __global__ __launch_bounds__(NTHREADS)
 void conv2d_bwd_weight_kernel(const bf16_t* __restrict__ dy,
                               const bf16_t* __restrict__ x,
                               float* __restrict__ ws, ConvGeom g, int M,
-                              int CRS, int slice_len, int fast_a) {
+                              int CRS, int slice_len) {
   __shared__ bf16_t lds[WLDS_ELEMS];
   const int rs0 = blockIdx.x * WBM;
   const int ko0 = blockIdx.y * BN;
@@ -939,23 +937,6 @@ void conv2d_bwd_weight_kernel(const bf16_t* __restrict__ dy,
         if (row < CRS && col < g.K)
           ws[slab + (long)row * g.K + col] = acc[mr][nr][r];
       }
-}
-
-// scatter a parity-class sub-grid result dxs (N,H2,W2,C) into
-// dx[:, ph::2, pw::2, :] (stride-2 bwd-data parity decomposition)
-__global__ __launch_bounds__(NTHREADS)
-void parity_scatter_kernel(const bf16_t* __restrict__ dxs,
-                           bf16_t* __restrict__ dx, int H, int W, int C,
-                           int ph, int pw, int H2, int W2, long total_sub) {
-  long i = (long)blockIdx.x * NTHREADS + threadIdx.x;
-  if (i >= total_sub) return;
-  int c = (int)(i % C);
-  long rest = i / C;
-  int w2 = (int)(rest % W2);
-  rest /= W2;
-  int h2 = (int)(rest % H2);
-  int n = (int)(rest / H2);
-  dx[(((long)n * H + ph + 2 * h2) * W + pw + 2 * w2) * C + c] = dxs[i];
 }
 
 // tiny-C (stem) im2col: col (M, CRSpad) bf16, one thread per (m, r*S+s)
@@ -1545,41 +1526,144 @@ void conv2d_bwd_weight_v2_kernel(const bf16_t* __restrict__ dy,
 
 // ============================== launchers ==============================
 
-#include <stdlib.h>
 #include <stdio.h>
+
+// ------------------------------------------------------- environment knobs
+// docs/knobs.md. Each is read once per process; a knob's special values are
+// mapped right where it is read.
+#define KNOB_NEVER (1 << 30)
 
 // BKT=64 halves barriers but its 55 KB LDS halves occupancy (2 vs 4 blocks/CU)
 // — the crossover is empirical, so the threshold is runtime-tunable.
 static int bk64_min_crs() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_CONV_BK64_MIN");
-    v = e ? atoi(e) : 512;
-    if (v <= 0) v = 1 << 30;  // 0 disables BKT=64
-  }
+  static const int v = env_int("CILFW_CONV_BK64_MIN", 512);
+  return v > 0 ? v : KNOB_NEVER;  // 0 disables BKT=64
+}
+
+// above this many blocks, BKT=32's higher occupancy wins
+static int bk64_max_blocks() {
+  static const int v = env_int("CILFW_CONV_BK64_MAXBLOCKS", 768);
   return v;
 }
 
-static int bk64_max_blocks() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_CONV_BK64_MAXBLOCKS");
-    v = e ? atoi(e) : 768;  // above this, BKT=32's higher occupancy wins
-  }
+static int ksplit_target() {
+  static const int v = env_int("CILFW_CONV_KSPLIT_TARGET", 512);
+  return v;
+}
+
+static int dw_target() {  // swept 256-2048: 1024 best (41.3k bench)
+  static const int v = env_int("CILFW_CONV_DW_TARGET", 1024);
+  return v;
+}
+
+static int conv_v2_enabled() {
+  static const int v = env_int("CILFW_CONV_V2", 1);
+  return v;
+}
+
+// bwd-data v2 measured slower than v1 on the CIFAR shapes (l1 pair 129 vs
+// 126 us, l3 139 vs 126) but ahead on the large-M ImageNet layers; route by
+// M with an env override (CILFW_CONV_V2_BWD_MINM, 0 disables).
+static int conv_v2_bwd_minm() {
+  static const int v = env_int("CILFW_CONV_V2_BWD_MINM", 150000);
+  return v == 0 ? KNOB_NEVER : v;
+}
+
+// measured: BM=256 loses to BM=128's occupancy at every ResNet shape — off
+// (0) by default
+static int fwd_bm256_min_m() {
+  static const int v = env_int("CILFW_CONV_BM256_MIN", 0);
+  return v > 0 ? v : KNOB_NEVER;
+}
+
+// A 128-wide v2 N-tile (2x the MFMA per staged A-byte at 2 blocks/CU) for
+// K >= 128 when the grid still fills the chip; 0 turns it off.
+static int v2_bn128_enabled() {
+  static const int v = env_int("CILFW_CONV_V2_BN128", 1);
+  return v;
+}
+
+// BN=128 wins only where the A-gather is trivial (1x1 convs: rn50_1x1
+// 173->218 TF); on the CIFAR 3x3 layers the halved occupancy loses
+// (l2 348->318 at M=32768) — this knob opens the tile to 3x3 layers at/above
+// that M (experiment; default -1 = never)
+static int v2_bn128_min3x3() {
+  static const int v = env_int("CILFW_CONV_V2_BN128_MIN3X3", -1);
+  return v >= 0 ? v : KNOB_NEVER;
+}
+
+static int s2_fused_enabled() {  // presence-only: any value disables
+  static const int v = !env_set("CILFW_NO_S2_FUSED");
+  return v;
+}
+
+// measured OFF-better on both rn18-CIFAR (41.2k vs 40.6k imgs/s) and
+// rn50@224 (4.57k vs 4.55k): the epilogue's two per-element scalar bf16
+// reads (mask y + BN input x, column-strided against the acc layout) cost
+// more inside the critical-path MFMA kernel than the standalone
+// (fully-vectorized) bn_bwd_sums pass they replace. Kept env-gated.
+static int bnbwd_fuse_enabled() {
+  static const int v = env_int("CILFW_BNBWD_FUSE", 0);
   return v;
 }
 
 static int pick_ksplit(int nblocks, int nk) {
   // aim for >= target workgroups without shredding the K loop
-  static int target = -1;
-  if (target < 0) {
-    const char* e = getenv("CILFW_CONV_KSPLIT_TARGET");
-    target = e ? atoi(e) : 512;
-  }
   int ks = 1;
-  while (ks < 8 && nblocks * ks < target && nk / (ks * 2) >= 4) ks *= 2;
+  while (ks < 8 && nblocks * ks < ksplit_target() && nk / (ks * 2) >= 4)
+    ks *= 2;
   return ks;
 }
+
+// ----------------------------------------------------------- slab reduce
+static dim3 reduce_slabs_grid(long len) {
+  return dim3((unsigned)((len + NTHREADS * 4 - 1) / (NTHREADS * 4)));
+}
+
+// split-K epilogue: sums the fp32 slabs into the bf16 output. With
+// ksplit == 1 the MFMA kernel stored bf16 itself and nothing is launched.
+static void launch_reduce_slabs_bf16(const void* ws, void* out, int ksplit,
+                                     long len, void* stream) {
+  if (ksplit <= 1) return;
+  hipLaunchKernelGGL(reduce_slabs_bf16_kernel, reduce_slabs_grid(len),
+                     dim3(NTHREADS), 0, (hipStream_t)stream,
+                     (const float*)ws, (bf16_t*)out, ksplit, len);
+}
+
+// bwd-weight always goes through slabs (nslices may be 1)
+static void launch_reduce_slabs_f32(const void* ws, void* out, int nslices,
+                                    long len, int accum, void* stream) {
+  hipLaunchKernelGGL(reduce_slabs_f32_kernel, reduce_slabs_grid(len),
+                     dim3(NTHREADS), 0, (hipStream_t)stream,
+                     (const float*)ws, (float*)out, nslices, len, accum);
+}
+
+// ------------------------------------------------------- kernel dispatch
+typedef void (*FwdV1Kernel)(const bf16_t*, const bf16_t*, bf16_t*, float*,
+                            ConvGeom, int, int, int, int);
+// [tile: 0 = BK32 x BM128, 1 = BK64 x BM128, 2 = BK32 x BM256][FAST]
+static const FwdV1Kernel kFwdV1[3][2] = {
+    {conv2d_fwd_kernel<32, 128, BN, false>,
+     conv2d_fwd_kernel<32, 128, BN, true>},
+    {conv2d_fwd_kernel<64, 128, BN, false>,
+     conv2d_fwd_kernel<64, 128, BN, true>},
+    {conv2d_fwd_kernel<32, 256, BN, false>,
+     conv2d_fwd_kernel<32, 256, BN, true>}};
+
+typedef void (*BwdDataKernel)(const bf16_t*, const bf16_t*, bf16_t*, float*,
+                              ConvGeom, int, int, int, int, const bf16_t*,
+                              const bf16_t*, const float*, const float*,
+                              float*, int);
+// [BKT == 64][FAST][BNP]
+static const BwdDataKernel kBwdData[2][2][2] = {
+    {{conv2d_bwd_data_kernel<32, false, false>,
+      conv2d_bwd_data_kernel<32, false, true>},
+     {conv2d_bwd_data_kernel<32, true, false>,
+      conv2d_bwd_data_kernel<32, true, true>}},
+    {{conv2d_bwd_data_kernel<64, false, false>,
+      conv2d_bwd_data_kernel<64, false, true>},
+     {conv2d_bwd_data_kernel<64, true, false>,
+      conv2d_bwd_data_kernel<64, true, true>}}};
 
 extern "C" {
 
@@ -1598,38 +1682,6 @@ static void* zpage_ptr() {
     p = q;
   }
   return p;
-}
-
-static int conv_v2_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_CONV_V2");
-    v = e ? atoi(e) : 1;
-  }
-  return v;
-}
-
-// bwd-data v2 measured slower than v1 on the CIFAR shapes (l1 pair 129 vs
-// 126 us, l3 139 vs 126) but ahead on the large-M ImageNet layers; route by
-// M with an env override (CILFW_CONV_V2_BWD_MINM, 0 disables).
-static int conv_v2_bwd_minm() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_CONV_V2_BWD_MINM");
-    v = e ? atoi(e) : 150000;
-    if (v == 0) v = 1 << 30;
-  }
-  return v;
-}
-
-static int fwd_bm256_min_m() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_CONV_BM256_MIN");
-    v = e ? atoi(e) : 0;  // measured: BM=256 loses to BM=128's occupancy at
-    if (v <= 0) v = 1 << 30;  // every ResNet shape — off by default
-  }
-  return v;
 }
 
 // ------------------------------------------------------------ route codes
@@ -1653,25 +1705,9 @@ static int fwd_route(int M, int C, int K, int R, int S, int ksplit,
   int CRS = C * R * S;
   int bm = fwd_bm(M);
   if (have_zp && fwd_v2_eligible(C) && bm == BM) {
-    // all-glds 2-phase kernel (v2): BK=64, tr_b16 B operand. A 128-wide
-    // N-tile (2x the MFMA per staged A-byte at 2 blocks/CU) for K >= 128
-    // when the grid still fills the chip; env CILFW_CONV_V2_BN128=0 off.
-    static int bn128 = -1;
-    if (bn128 < 0) {
-      const char* e = getenv("CILFW_CONV_V2_BN128");
-      bn128 = e ? atoi(e) : 1;
-    }
-    // BN=128 wins only where the A-gather is trivial (1x1 convs: rn50_1x1
-    // 173->218 TF); on the CIFAR 3x3 layers the halved occupancy loses
-    // (l2 348->318 at M=32768) — env CILFW_CONV_V2_BN128_MIN3X3 opens the
-    // tile to 3x3 layers at/above that M (experiment; default off)
-    static int min3x3 = -2;
-    if (min3x3 == -2) {
-      const char* e = getenv("CILFW_CONV_V2_BN128_MIN3X3");
-      min3x3 = e ? atoi(e) : -1;  // -1 = never
-    }
-    int shape_ok = (R == 1 && S == 1) || (min3x3 >= 0 && M >= min3x3);
-    if (bn128 && K % 128 == 0 && shape_ok &&
+    // all-glds 2-phase kernel (v2): BK=64, tr_b16 B operand
+    int shape_ok = (R == 1 && S == 1) || M >= v2_bn128_min3x3();
+    if (v2_bn128_enabled() && K % 128 == 0 && shape_ok &&
         cdiv(M, BM) * cdiv(K, 128) * ksplit >= 256)
       return FWD_V2_BN128;
     return FWD_V2_BN64;
@@ -1691,6 +1727,12 @@ int cilfw_conv2d_fwd_route(int N, int C, int K, int R, int S, int Ho, int Wo,
   return fwd_route(N * Ho * Wo, C, K, R, S, ksplit, 1);
 }
 
+// rows of the (gy, 2, K) BN-statistics partials the v2 forward epilogue
+// writes: one per M block
+int cilfw_conv2d_fwd_bn_gy(int N, int Ho, int Wo) {
+  return cdiv(N * Ho * Wo, BM);
+}
+
 void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
                       int N, int H, int W, int C, int K, int R, int S,
                       int stride, int pad, int Ho, int Wo, int ksplit,
@@ -1699,91 +1741,38 @@ void cilfw_conv2d_fwd(const void* x, const void* w, void* y, void* ws,
              0, 0, magic40(C), magic40(S)};
   int M = N * Ho * Wo;
   int CRS = C * R * S;
-  int fast_a = (C % 16 == 0);
   void* zp = fwd_v2_eligible(C) ? zpage_ptr() : nullptr;
   int route = fwd_route(M, C, K, R, S, ksplit, zp != nullptr);
   if (route == FWD_V2_BN128 || route == FWD_V2_BN64) {
-    int nk2 = cdiv(CRS, V2BK);
-    int bn2 = route == FWD_V2_BN128 ? 128 : BN;
-    dim3 grid2(cdiv(M, BM), cdiv(K, bn2), ksplit);
-    float* parts = (float*)(ksplit > 1 ? nullptr : bn_parts);
-    if (route == FWD_V2_BN128)
-      hipLaunchKernelGGL(conv2d_fwd_v2_kernel<128>, grid2, dim3(NTHREADS),
-                         0, (hipStream_t)stream, (const bf16_t*)x,
-                         (const bf16_t*)w, (bf16_t*)y, (float*)ws,
-                         (const bf16_t*)zp, g, M, CRS, nk2, ksplit, parts);
-    else
-      hipLaunchKernelGGL(conv2d_fwd_v2_kernel<BN>, grid2, dim3(NTHREADS), 0,
-                         (hipStream_t)stream, (const bf16_t*)x,
-                         (const bf16_t*)w, (bf16_t*)y, (float*)ws,
-                         (const bf16_t*)zp, g, M, CRS, nk2, ksplit, parts);
-    if (ksplit > 1) {
-      long len = (long)M * K;
-      hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                         dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                         dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                         (bf16_t*)y, ksplit, len);
-    }
-    return;
+    int bn128 = route == FWD_V2_BN128;
+    dim3 grid(cdiv(M, BM), cdiv(K, bn128 ? 128 : BN), ksplit);
+    hipLaunchKernelGGL(
+        bn128 ? conv2d_fwd_v2_kernel<128> : conv2d_fwd_v2_kernel<BN>, grid,
+        dim3(NTHREADS), 0, (hipStream_t)stream, (const bf16_t*)x,
+        (const bf16_t*)w, (bf16_t*)y, (float*)ws, (const bf16_t*)zp, g, M,
+        CRS, cdiv(CRS, V2BK), ksplit,
+        (float*)(ksplit > 1 ? nullptr : bn_parts));
+  } else {
+    int bm = fwd_bm(M);
+    int tile = route == FWD_V1_BK64 ? 1 : (bm == 256 ? 2 : 0);
+    dim3 grid(cdiv(M, bm), cdiv(K, BN), ksplit);
+    hipLaunchKernelGGL(kFwdV1[tile][C % 16 == 0], grid, dim3(NTHREADS), 0,
+                       (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)w, (bf16_t*)y, (float*)ws, g, M, CRS,
+                       cdiv(CRS, tile == 1 ? 64 : 32), ksplit);
   }
-  int bm = fwd_bm(M);
-  int nk = cdiv(CRS, route == FWD_V1_BK64 ? 64 : 32);
-  dim3 grid(cdiv(M, bm), cdiv(K, BN), ksplit);
-#define LAUNCH_FWD(BKT_, BM_)                                                 \
-  do {                                                                        \
-    if (fast_a)                                                               \
-      hipLaunchKernelGGL((conv2d_fwd_kernel<BKT_, BM_, BN, true>), grid,      \
-                         dim3(NTHREADS), 0, (hipStream_t)stream,              \
-                         (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y,      \
-                         (float*)ws, g, M, CRS, nk, fast_a, ksplit);          \
-    else                                                                      \
-      hipLaunchKernelGGL((conv2d_fwd_kernel<BKT_, BM_, BN, false>), grid,     \
-                         dim3(NTHREADS), 0, (hipStream_t)stream,              \
-                         (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y,      \
-                         (float*)ws, g, M, CRS, nk, fast_a, ksplit);          \
-  } while (0)
-  if (route == FWD_V1_BK64)
-    LAUNCH_FWD(64, 128);
-  else if (bm == 256)
-    LAUNCH_FWD(32, 256);
-  else
-    LAUNCH_FWD(32, 128);
-#undef LAUNCH_FWD
-  if (ksplit > 1) {
-    long len = (long)M * K;
-    hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                       dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                       dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                       (bf16_t*)y, ksplit, len);
-  }
+  launch_reduce_slabs_bf16(ws, y, ksplit, (long)M * K, stream);
 }
 
 int cilfw_conv2d_fwd_ksplit(int N, int C, int K, int R, int S, int Ho,
                             int Wo) {
-  int M = N * Ho * Wo;
-  int CRS = C * R * S;
-  int nk = cdiv(CRS, 32);
-  return pick_ksplit(cdiv(M, BM) * cdiv(K, BN), nk);
+  return pick_ksplit(cdiv(N * Ho * Wo, BM) * cdiv(K, BN),
+                     cdiv(C * R * S, 32));
 }
 
-static int bnbwd_fuse_enabled() {
-  // measured OFF-better on both rn18-CIFAR (41.2k vs 40.6k imgs/s) and
-  // rn50@224 (4.57k vs 4.55k): the epilogue's two per-element scalar bf16
-  // reads (mask y + BN input x, column-strided against the acc layout) cost
-  // more inside the critical-path MFMA kernel than the standalone
-  // (fully-vectorized) bn_bwd_sums pass they replace. Kept env-gated:
-  // CILFW_BNBWD_FUSE=1.
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("CILFW_BNBWD_FUSE");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
+// ops/functional.py asks this instead of reading the knob a second time
+int cilfw_bnbwd_fuse_enabled() { return bnbwd_fuse_enabled() != 0; }
 
-// exact predicate for "bwd-data will take the v1 ksplit==1 path and can emit
-// BN-backward partials" — Python checks this before allocating the parts
-// buffer; the launcher re-checks and reports what it actually did
 static int bwd_data_v2_eligible(int M, int K, int stride) {
   return K % 8 == 0 && stride <= 2 && conv_v2_enabled() &&
          M >= conv_v2_bwd_minm();
@@ -1798,8 +1787,7 @@ static int bwd_data_route(int N, int H, int W, int C, int K, int R, int S,
   // small per-class grids fall back to the single zero-structured kernel
   // (its ksplit fills the chip better there — measured)
   if (stride == 2 && (R > 1 || S > 1) && K % 16 == 0 &&
-      cdiv(Mc, BM) * cdiv(C, BN) >= 128 &&
-      getenv("CILFW_NO_S2_FUSED") == nullptr)
+      cdiv(Mc, BM) * cdiv(C, BN) >= 128 && s2_fused_enabled())
     return BWDD_S2_FUSED;
   int M = N * H * W;
   if (have_zp && bwd_data_v2_eligible(M, K, stride)) return BWDD_V2;
@@ -1814,11 +1802,18 @@ int cilfw_conv2d_bwd_data_route(int N, int H, int W, int C, int K, int R,
   return bwd_data_route(N, H, W, C, K, R, S, stride, ksplit, 1);
 }
 
+int cilfw_conv2d_bwd_data_ksplit(int N, int H, int W, int C, int K, int R,
+                                 int S) {
+  return pick_ksplit(cdiv(N * H * W, BM) * cdiv(C, BN), cdiv(R * S * K, 32));
+}
+
+// exact predicate for "bwd-data will take the v1 ksplit==1 path and can emit
+// BN-backward partials" — Python checks this before allocating the parts
+// buffer; the launcher re-checks and reports what it actually did
 int cilfw_conv2d_bwd_data_can_fuse_bn(int N, int H, int W, int C, int K,
                                       int R, int S, int stride) {
   if (!bnbwd_fuse_enabled() || stride != 1) return 0;
-  int ks = pick_ksplit(cdiv(N * H * W, BM) * cdiv(C, BN),
-                       cdiv(R * S * K, 32));
+  int ks = cilfw_conv2d_bwd_data_ksplit(N, H, W, C, K, R, S);
   // v2 all-glds kernel has no BN epilogue (yet)
   int route = bwd_data_route(N, H, W, C, K, R, S, stride, ks, 1);
   return (route == BWDD_V1_BK32 || route == BWDD_V1_BK64) && ks == 1;
@@ -1828,6 +1823,7 @@ int cilfw_conv2d_bwd_data_bn_gy(int N, int H, int W) {
   return cdiv(N * H * W, BM);
 }
 
+// returns 1 when the BN-backward partials were written to bn_parts
 int cilfw_conv2d_bwd_data(const void* dy, const void* w, void* dx, void* ws,
                           int N, int H, int W, int C, int K, int R, int S,
                           int stride, int pad, int Ho, int Wo, int ksplit,
@@ -1850,130 +1846,31 @@ int cilfw_conv2d_bwd_data(const void* dy, const void* w, void* dx, void* ws,
                        (const bf16_t*)w, (bf16_t*)dx, g);
     return 0;
   }
-  int fast_a = (K % 16 == 0) && stride <= 2;  // FAST path shift-divides
+  dim3 grid(cdiv(M, BM), cdiv(C, BN), ksplit);
+  int bnp = 0;
   if (route == BWDD_V2) {  // all-glds 2-phase kernel (v2)
-    int nk2 = cdiv(RSK, V2BK);
-    dim3 grid2(cdiv(M, BM), cdiv(C, BN), ksplit);
-    hipLaunchKernelGGL(conv2d_bwd_data_v2_kernel, grid2, dim3(NTHREADS), 0,
+    hipLaunchKernelGGL(conv2d_bwd_data_v2_kernel, grid, dim3(NTHREADS), 0,
                        (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)w, (bf16_t*)dx, (float*)ws,
-                       (const bf16_t*)zp, g, M, RSK, nk2, ksplit);
-    if (ksplit > 1) {
-      long len = (long)M * C;
-      hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                         dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                         dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                         (bf16_t*)dx, ksplit, len);
-    }
-    return 0;
-  }
-  int use64 = route == BWDD_V1_BK64;
-  int nk = cdiv(RSK, use64 ? 64 : 32);
-  dim3 grid(cdiv(M, BM), cdiv(C, BN), ksplit);
-  // BN-backward partial-sum epilogue: only the ksplit==1 v1 path materializes
-  // final dx inside the MFMA kernel (split-K writes fp32 slabs instead)
-  int bnp = bn_parts != nullptr && ksplit == 1 && stride == 1 &&
-            bnbwd_fuse_enabled();
-#define LAUNCH_BWD_DATA(BKT_, FAST_, BNP_)                                    \
-  hipLaunchKernelGGL((conv2d_bwd_data_kernel<BKT_, FAST_, BNP_>), grid,       \
-                     dim3(NTHREADS), 0, (hipStream_t)stream,                  \
-                     (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx,        \
-                     (float*)ws, g, M, RSK, nk, fast_a, ksplit,               \
-                     (const bf16_t*)bn_y, (const bf16_t*)bn_x,                \
-                     (const float*)bn_mean, (const float*)bn_invstd,          \
-                     (float*)bn_parts, bn_relu)
-  if (bnp) {
-    if (use64 && fast_a) LAUNCH_BWD_DATA(64, true, true);
-    else if (use64) LAUNCH_BWD_DATA(64, false, true);
-    else if (fast_a) LAUNCH_BWD_DATA(32, true, true);
-    else LAUNCH_BWD_DATA(32, false, true);
-    return 1;
-  }
-  if (use64 && fast_a) LAUNCH_BWD_DATA(64, true, false);
-  else if (use64) LAUNCH_BWD_DATA(64, false, false);
-  else if (fast_a) LAUNCH_BWD_DATA(32, true, false);
-  else LAUNCH_BWD_DATA(32, false, false);
-#undef LAUNCH_BWD_DATA
-  if (ksplit > 1) {
-    long len = (long)M * C;
-    hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                       dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                       dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                       (bf16_t*)dx, ksplit, len);
-  }
-  return 0;
-}
-
-void cilfw_conv2d_bwd_data_sub(const void* dy, const void* w, void* dx,
-                               void* ws, int N, int H, int W, int C, int K,
-                               int R, int S, int padh, int padw, int Ho,
-                               int Wo, int ksplit, void* stream) {
-  // stride-1 sub-problem of the parity decomposition (asymmetric pads)
-  ConvGeom g{N, H, W, C, K, R, S, 1, padh, padw, Ho, Wo,
-             0, 0, magic40(K), magic40(S)};
-  int M = N * H * W;
-  int RSK = R * S * K;
-  int fast_a = (K % 16 == 0);  // stride fixed at 1 here
-  void* zp = bwd_data_v2_eligible(M, K, 1) ? zpage_ptr() : nullptr;
-  int route = bwd_data_route(N, H, W, C, K, R, S, 1, ksplit, zp != nullptr);
-  if (route == BWDD_V2) {  // all-glds 2-phase kernel (v2)
-    int nk2 = cdiv(RSK, V2BK);
-    dim3 grid2(cdiv(M, BM), cdiv(C, BN), ksplit);
-    hipLaunchKernelGGL(conv2d_bwd_data_v2_kernel, grid2, dim3(NTHREADS), 0,
+                       (const bf16_t*)zp, g, M, RSK, cdiv(RSK, V2BK), ksplit);
+  } else {
+    int bk64 = route == BWDD_V1_BK64;
+    int fast = (K % 16 == 0) && stride <= 2;  // FAST path shift-divides
+    // BN-backward partial-sum epilogue: only the ksplit==1 v1 path
+    // materializes final dx inside the MFMA kernel (split-K writes fp32
+    // slabs instead)
+    bnp = bn_parts != nullptr && ksplit == 1 && stride == 1 &&
+          bnbwd_fuse_enabled();
+    hipLaunchKernelGGL(kBwdData[bk64][fast][bnp], grid, dim3(NTHREADS), 0,
                        (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)w, (bf16_t*)dx, (float*)ws,
-                       (const bf16_t*)zp, g, M, RSK, nk2, ksplit);
-    if (ksplit > 1) {
-      long len = (long)M * C;
-      hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                         dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                         dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                         (bf16_t*)dx, ksplit, len);
-    }
-    return;
+                       (const bf16_t*)w, (bf16_t*)dx, (float*)ws, g, M, RSK,
+                       cdiv(RSK, bk64 ? 64 : 32), ksplit,
+                       (const bf16_t*)bn_y, (const bf16_t*)bn_x,
+                       (const float*)bn_mean, (const float*)bn_invstd,
+                       (float*)bn_parts, bn_relu);
   }
-  int use64 = route == BWDD_V1_BK64;
-  int nk = cdiv(RSK, use64 ? 64 : 32);
-  dim3 grid(cdiv(M, BM), cdiv(C, BN), ksplit);
-#define LAUNCH_BWD_DATA_SUB(BKT_, FAST_)                                       \
-  hipLaunchKernelGGL((conv2d_bwd_data_kernel<BKT_, FAST_, false>), grid,      \
-                     dim3(NTHREADS), 0, (hipStream_t)stream,                  \
-                     (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx,        \
-                     (float*)ws, g, M, RSK, nk, fast_a, ksplit,               \
-                     (const bf16_t*)nullptr, (const bf16_t*)nullptr,          \
-                     (const float*)nullptr, (const float*)nullptr,            \
-                     (float*)nullptr, 0)
-  if (use64 && fast_a) LAUNCH_BWD_DATA_SUB(64, true);
-  else if (use64) LAUNCH_BWD_DATA_SUB(64, false);
-  else if (fast_a) LAUNCH_BWD_DATA_SUB(32, true);
-  else LAUNCH_BWD_DATA_SUB(32, false);
-#undef LAUNCH_BWD_DATA_SUB
-  if (ksplit > 1) {
-    long len = (long)M * C;
-    hipLaunchKernelGGL(reduce_slabs_bf16_kernel,
-                       dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                       dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                       (bf16_t*)dx, ksplit, len);
-  }
-}
-
-void cilfw_parity_scatter(const void* dxs, void* dx, int N, int H, int W,
-                          int C, int ph, int pw, int H2, int W2,
-                          void* stream) {
-  long total = (long)N * H2 * W2 * C;
-  hipLaunchKernelGGL(parity_scatter_kernel,
-                     dim3((int)cdiv((long)total, (long)NTHREADS)),
-                     dim3(NTHREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)dxs, (bf16_t*)dx, H, W, C, ph, pw, H2,
-                     W2, total);
-}
-
-int cilfw_conv2d_bwd_data_ksplit(int N, int H, int W, int C, int K, int R,
-                                 int S) {
-  int M = N * H * W;
-  int RSK = R * S * K;
-  int nk = cdiv(RSK, 32);
-  return pick_ksplit(cdiv(M, BM) * cdiv(C, BN), nk);
+  launch_reduce_slabs_bf16(ws, dx, ksplit, (long)M * C, stream);
+  return bnp;
 }
 
 static int bwd_weight_v2_eligible(int C, int K, int accum) {
@@ -1995,11 +1892,10 @@ int cilfw_conv2d_bwd_weight_route(int N, int C, int K, int R, int S, int Ho,
   return bwd_weight_route(C, K, accum, 1);
 }
 
-void cilfw_conv2d_bwd_weight(const void* dy, const void* x, const void* mt,
-                             void* dw, void* ws, int N, int H, int W, int C,
-                             int K, int R, int S, int stride, int pad, int Ho,
+void cilfw_conv2d_bwd_weight(const void* dy, const void* x, void* dw,
+                             void* ws, int N, int H, int W, int C, int K,
+                             int R, int S, int stride, int pad, int Ho,
                              int Wo, int nslices, int accum, void* stream) {
-  (void)mt;  // kept in the ABI for the (cached) im2col table experiments
   ConvGeom g{N, H, W, C, K, R, S, stride, pad, pad, Ho, Wo,
              magic40(Ho * Wo), magic40(Wo), magic40(C), magic40(S)};
   int M = N * Ho * Wo;
@@ -2009,39 +1905,23 @@ void cilfw_conv2d_bwd_weight(const void* dy, const void* x, const void* mt,
     abort();
   }
   int CRS = C * R * S;
-  int slice_len = cdiv(M, nslices);
-  slice_len = cdiv(slice_len, WBK) * WBK;
-  int fast_a = (C % 8 == 0);
+  int slice_len = cdiv(cdiv(M, nslices), WBK) * WBK;
   dim3 grid(cdiv(CRS, WBM), cdiv(K, BN), nslices);
   void* zp = bwd_weight_v2_eligible(C, K, accum) ? zpage_ptr() : nullptr;
   int route = bwd_weight_route(C, K, accum, zp != nullptr);
-  if (route == BWDW_V2) {  // all-glds 2-phase kernel (v2)
+  if (route == BWDW_V2)  // all-glds 2-phase kernel (v2)
     hipLaunchKernelGGL(conv2d_bwd_weight_v2_kernel, grid, dim3(NTHREADS), 0,
                        (hipStream_t)stream, (const bf16_t*)dy,
                        (const bf16_t*)x, (float*)ws, (const bf16_t*)zp, g,
                        M, CRS, slice_len);
-    long len2 = (long)CRS * K;
-    hipLaunchKernelGGL(reduce_slabs_f32_kernel,
-                       dim3((int)cdiv((long)len2, (long)NTHREADS * 4)),
-                       dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                       (float*)dw, nslices, len2, accum);
-    return;
-  }
-  if (route == BWDW_V1_FAST)
-    hipLaunchKernelGGL(conv2d_bwd_weight_kernel<true>, grid, dim3(NTHREADS),
-                       0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, (float*)ws, g, M, CRS, slice_len,
-                       fast_a);
   else
-    hipLaunchKernelGGL(conv2d_bwd_weight_kernel<false>, grid, dim3(NTHREADS),
-                       0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)x, (float*)ws, g, M, CRS, slice_len,
-                       fast_a);
-  long len = (long)CRS * K;
-  hipLaunchKernelGGL(reduce_slabs_f32_kernel,
-                     dim3((int)cdiv((long)len, (long)NTHREADS * 4)),
-                     dim3(NTHREADS), 0, (hipStream_t)stream, (float*)ws,
-                     (float*)dw, nslices, len, accum);
+    hipLaunchKernelGGL(route == BWDW_V1_FAST
+                           ? conv2d_bwd_weight_kernel<true>
+                           : conv2d_bwd_weight_kernel<false>,
+                       grid, dim3(NTHREADS), 0, (hipStream_t)stream,
+                       (const bf16_t*)dy, (const bf16_t*)x, (float*)ws, g, M,
+                       CRS, slice_len);
+  launch_reduce_slabs_f32(ws, dw, nslices, (long)CRS * K, accum, stream);
 }
 
 void cilfw_im2col_smallc(const void* x, const void* mt, void* col,
@@ -2070,12 +1950,7 @@ int cilfw_conv2d_bwd_weight_nslices(int N, int C, int K, int R, int S,
   int M = N * Ho * Wo;
   int CRS = C * R * S;
   int nblocks = cdiv(CRS, WBM) * cdiv(K, BN);
-  static int target = -1;
-  if (target < 0) {
-    const char* e = getenv("CILFW_CONV_DW_TARGET");
-    target = e ? atoi(e) : 1024;  // swept 256-2048: 1024 best (41.3k bench)
-  }
-  int ns = cdiv(target, max(nblocks, 1));
+  int ns = cdiv(dw_target(), max(nblocks, 1));
   int max_ns = max(cdiv(M, WBK * 8), 1);  // keep >= 8 K-steps per slice
   if (ns > max_ns) ns = max_ns;
   if (ns < 1) ns = 1;

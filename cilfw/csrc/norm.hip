@@ -640,7 +640,15 @@ void stride_scatter_kernel(const bf16_t* __restrict__ dxs,
 
 // ============================== launchers ==============================
 
+#define BN_ROWS_PER_BLK 256
+
 extern "C" {
+
+// row blocks (grid.y) of bn_sums / bn_bwd_sums: the wrappers size the
+// [gy][2][C] partials scratch with it
+int cilfw_bn_sums_gy(long M) {
+  return cdiv((int)min(M, (long)INT32_MAX), BN_ROWS_PER_BLK);
+}
 
 void cilfw_bn_fwd(const void* x, void* y, const void* res,
                   const void* gamma, const void* beta,
@@ -661,13 +669,12 @@ void cilfw_bn_fwd(const void* x, void* y, const void* res,
                        C, momentum, eps);
   } else if (training) {
     // scratch_sums: [gy][2][C] partials + [2][C] reduced (see wrapper sizing)
-    int rows_per_blk = 256;
-    dim3 grid(cdiv(C, 64), cdiv((int)min(M, (long)INT32_MAX), rows_per_blk));
+    dim3 grid(cdiv(C, 64), cilfw_bn_sums_gy(M));
     float* part = (float*)scratch_sums;
     float* sum = part + (long)grid.y * 2 * C;
     float* sumsq = sum + C;
     hipLaunchKernelGGL(bn_sums_kernel, grid, dim3(NT), 0, st,
-                       (const bf16_t*)x, part, M, C, rows_per_blk);
+                       (const bf16_t*)x, part, M, C, BN_ROWS_PER_BLK);
     hipLaunchKernelGGL(bn_reduce_slabs_kernel,
                        dim3(cdiv(2 * C, NT / WAVE)), dim3(NT), 0, st, part,
                        sum, (int)grid.y, (long)2 * C, (float*)nullptr,
@@ -717,8 +724,7 @@ void cilfw_bn_bwd(const void* dy, const void* x, const void* y, void* dx,
   // sums pass and its 3-stream re-read of (dy, x, y) are skipped; dgb then
   // only needs room for the reduced [dgamma | dbeta].
   hipStream_t st = (hipStream_t)stream;
-  int rows_per_blk = 256;
-  dim3 grid(cdiv(C, 64), cdiv((int)min(M, (long)INT32_MAX), rows_per_blk));
+  dim3 grid(cdiv(C, 64), cilfw_bn_sums_gy(M));
   int gy = ext_part ? ext_gy : (int)grid.y;
   long red_off = ext_part ? 0 : (long)grid.y * 2 * C;
   float* part = ext_part ? (float*)ext_part : (float*)dgb;
@@ -728,7 +734,7 @@ void cilfw_bn_bwd(const void* dy, const void* x, const void* y, void* dx,
     hipLaunchKernelGGL(bn_bwd_sums_kernel, grid, dim3(NT), 0, st,
                        (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)y,
                        (const float*)mean, (const float*)invstd, part,
-                       M, C, rows_per_blk, relu);
+                       M, C, BN_ROWS_PER_BLK, relu);
   hipLaunchKernelGGL(bn_reduce_slabs_kernel, dim3(cdiv(2 * C, NT / WAVE)),
                      dim3(NT), 0, st, part, dgamma, gy,
                      (long)2 * C, dbeta, (long)C);

@@ -18,7 +18,7 @@ cuBLAS kernels behind reference ``resnet.py`` and ``template.py:99-101, 259-263`
 import torch
 import torch.nn.functional as F
 
-from ._backend import use_hip, ext
+from ._backend import use_hip, ext, _load
 
 
 _wgrad_stream = None
@@ -53,7 +53,12 @@ def _sink_on():
 def _bnbwd_fuse_on():
     # default off: measured slower than the standalone vectorized sums pass
     # on both rn18 and rn50 (see conv.hip bnbwd_fuse_enabled) — the kernel
-    # path stays covered by tests either way and flips on via env
+    # path stays covered by tests either way and flips on via env. The
+    # extension, when built, is the knob's one reader; the CPU reference
+    # path has only the environment
+    E = _load()
+    if E is not None:
+        return E.bnbwd_fuse_enabled()
     import os
     return os.environ.get("CILFW_BNBWD_FUSE", "0") == "1"
 
@@ -113,8 +118,7 @@ class Conv2dNHWC(torch.autograd.Function):
             if parts is not None:
                 # a following training-mode BN consumes these instead of
                 # running its own bn_sums pass over y
-                y._cilfw_bn_parts = (parts, (y.numel() // y.shape[-1]
-                                             + 127) // 128)
+                y._cilfw_bn_parts = parts
             return y
         # CPU reference: fp32 NCHW conv
         xf = _to_nchw(x).float()
@@ -251,12 +255,10 @@ class BatchNormAct(torch.autograd.Function):
         ctx.b_ref = b_param if b_param is not None else beta
         ctx.sinked = g_param is not None
         if use_hip(x):
-            pg = getattr(x, "_cilfw_bn_parts", None)
             y, save_mean, save_invstd = ext().bn_fwd(
                 x, gamma, beta, running_mean, running_var,
                 momentum, eps, training, relu,
-                ext_parts=pg[0] if pg else None,
-                ext_gy=pg[1] if pg else 0)
+                ext_parts=getattr(x, "_cilfw_bn_parts", None))
             ctx.training = training
             ctx.save_for_backward(x, gamma, save_mean, save_invstd, y)
             if training and fuse_bwd and _bnbwd_fuse_on():
@@ -361,12 +363,10 @@ class BatchNormAddReLU(torch.autograd.Function):
         ctx.b_ref = b_param if b_param is not None else beta
         ctx.sinked = g_param is not None
         if use_hip(x):
-            pg = getattr(x, "_cilfw_bn_parts", None)
             y, save_mean, save_invstd = ext().bn_fwd(
                 x, gamma, beta, running_mean, running_var, momentum, eps,
                 training, True, residual=residual,
-                ext_parts=pg[0] if pg else None,
-                ext_gy=pg[1] if pg else 0)
+                ext_parts=getattr(x, "_cilfw_bn_parts", None))
             ctx.training = training
             ctx.save_for_backward(x, gamma, save_mean, save_invstd, y)
             return y

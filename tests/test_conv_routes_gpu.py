@@ -128,9 +128,10 @@ def test_conv_fwd_bn_stats_epilogue(N, H, W, C, K, k, st, pd, route):
 
     # the kernel sums the bf16-rounded stored y: independent of conv accuracy
     M = y.numel() // K
-    gy = (M + 127) // 128
+    gy = parts.shape[0]
+    assert parts.shape == (gy, 2, K)
     y64 = y.double().cpu().view(M, K)
-    got = parts.double().cpu().view(gy, 2, K).sum(0)
+    got = parts.double().cpu().sum(0)
     _within(got[0], (y64.sum(0), M * U * y64.abs().sum(0)), "parts sum")
     _within(got[1], ((y64 * y64).sum(0), M * U * (y64 * y64).sum(0)),
             "parts sumsq")
@@ -142,7 +143,7 @@ def test_conv_fwd_bn_stats_epilogue(N, H, W, C, K, k, st, pd, route):
     rv0 = torch.rand(K, generator=gen) + 0.5
     want = _bn_ref(y64, gamma.double(), beta.double(), rm0.double(),
                    rv0.double(), 0.1, 1e-5, True)
-    for tag, kw in (("ext_parts", dict(ext_parts=parts, ext_gy=gy)),
+    for tag, kw in (("ext_parts", dict(ext_parts=parts)),
                     ("own sums", {})):
         rm, rv = rm0.clone().cuda(), rv0.clone().cuda()
         out, mean, invstd = Hop.bn_fwd(y, gamma.cuda(), beta.cuda(), rm, rv,
@@ -234,7 +235,9 @@ _CHILD = textwrap.dedent("""
     import test_conv_routes_gpu as T
     mode = {mode!r}
     split = 0
-    for i, (N, Hh, W, C, K, k, st, pd) in enumerate(T.FUZZ):
+    ran_bwd, ran_fwd = set(), set()  # (route, FAST instantiation) launched
+    for i, (N, Hh, W, C, K, k, st, pd) in enumerate(
+            T.FUZZ if mode != "bnp" else ()):
         route, ks = H.conv2d_bwd_data_route(N, Hh, W, C, K, k, k, st)
         if mode == "v2":
             assert route == "v2", (route, T.FUZZ[i])
@@ -242,6 +245,7 @@ _CHILD = textwrap.dedent("""
         else:
             assert route in ("v1_bk32", "v1_bk64"), (route, T.FUZZ[i])
         T._check_bwd_data(H, N, Hh, W, C, K, k, st, pd, route, seed=50 + i)
+        ran_bwd.add((route, K % 16 == 0 and st <= 2))
         if mode == "v1":
             froute, fks = H.conv2d_fwd_route(N, Hh, W, C, K, k, k, st, pd)
             assert froute in ("v1_bk32", "v1_bk64"), (froute, T.FUZZ[i])
@@ -250,7 +254,40 @@ _CHILD = textwrap.dedent("""
             ref, mag, n = O.conv_fwd_ref(x, w, st, pd)
             O.check(y, ref, mag, n + (fks if fks > 1 else 0), True,
                     "fwd " + froute)
+            ran_fwd.add((froute, C % 16 == 0))
     assert mode != "v2" or split >= 2, "no split-K geometry reached v2"
+    if mode == "v1":
+        every = {{(r, f) for r in ("v1_bk32", "v1_bk64")
+                 for f in (True, False)}}
+        assert ran_bwd == every, ("bwd-data", sorted(every - ran_bwd))
+        assert ran_fwd == every, ("forward", sorted(every - ran_fwd))
+    for i, (N, Hh, W, C, K, route, fast) in enumerate(
+            T.BNP_SHAPES if mode == "bnp" else ()):
+        assert H.conv2d_bwd_data_route(N, Hh, W, C, K, 3, 3, 1) == (route, 1)
+        assert (K % 16 == 0) == fast
+        # ksplit == 1 store of the plain kernel against the fp64 oracle
+        T._check_bwd_data(H, N, Hh, W, C, K, 3, 1, 1, route, seed=90 + i)
+        torch.manual_seed(i)
+        dev = "cuda"
+        dy = torch.randn(N, Hh, W, K, device=dev).bfloat16() * 0.1
+        w = torch.randn(3, 3, C, K, device=dev).bfloat16() * 0.05
+        bn_x = torch.randn(N, Hh, W, C, device=dev).bfloat16()
+        bn_y = torch.randn(N, Hh, W, C, device=dev).bfloat16()  # ~half <= 0
+        mean = torch.randn(C, device=dev)
+        invstd = torch.rand(C, device=dev) + 0.5
+        gamma = torch.randn(C, device=dev)
+        dx0 = H.conv2d_bwd_data(dy, w, 1, 1, Hh, W)
+        dx1, parts = H.conv2d_bwd_data(dy, w, 1, 1, Hh, W,
+                                       bn_meta=(bn_y, bn_x, mean, invstd, 1))
+        assert parts is not None, "fusion did not engage"
+        assert parts.shape == (2, 2, C)  # ragged second row block
+        assert torch.equal(dx0, dx1), "dx changed under the BN epilogue"
+        a = H.bn_bwd(dx0, bn_x, gamma, mean, invstd, bn_y, True, True)
+        b = H.bn_bwd(dx0, bn_x, gamma, mean, invstd, bn_y, True, True,
+                     ext_parts=parts)
+        torch.cuda.synchronize()
+        for j in (1, 2):  # dgamma, dbeta
+            torch.testing.assert_close(a[j], b[j], rtol=2e-4, atol=2e-3)
     torch.cuda.synchronize()
     print("routes-child-ok")
 """)
@@ -281,6 +318,29 @@ def test_v1_kernels_forward_and_bwd_data():
     launch falls back to when the zero page is missing — forward and
     bwd-data over the same geometries."""
     _run_child("v1", {"CILFW_CONV_V2": "0"})
+
+
+# bwd-data with the BN-backward epilogue, one shape per instantiation of
+# conv2d_bwd_data_kernel<BKT, FAST, true> (3x3, stride 1, pad 1). M is 147,
+# 147, 175, 144: two row blocks each, the second ragged.
+BNP_SHAPES = [
+    # N, H, W, C, K, route, FAST
+    (3, 7, 7, 16, 16, "v1_bk32", True),
+    (3, 7, 7, 16, 24, "v1_bk32", False),    # K % 16 != 0
+    (7, 5, 5, 24, 64, "v1_bk64", True),     # RSK = 576
+    (4, 6, 6, 128, 72, "v1_bk64", False),   # RSK = 648, two C tiles
+]
+
+
+@pytest.mark.timeout(300)
+def test_bwd_data_bn_epilogue_every_instantiation():
+    """CILFW_BNBWD_FUSE=1 with CILFW_CONV_KSPLIT_TARGET=1 (ksplit == 1
+    everywhere): each BKT x FAST kernel with the epilogue gives the dx of
+    the plain kernel bit for bit, and partials that reduce to the BN grads
+    of the standalone sums pass (assertions and tolerances of
+    test_ops_gpu.py::test_bnbwd_fuse_partials_match_sums_pass)."""
+    _run_child("bnp", {"CILFW_BNBWD_FUSE": "1",
+                       "CILFW_CONV_KSPLIT_TARGET": "1"})
 
 
 # ------------------------------------------------- bwd-weight delivery
