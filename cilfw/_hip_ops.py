@@ -383,11 +383,15 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, training,
     _bf16(x, "bn_fwd.x")
     if residual is not None:
         _bf16(residual, "bn_fwd.residual")
+        # the apply kernel indexes the residual by x's extent
+        assert residual.shape == x.shape, \
+            f"bn_fwd: residual {tuple(residual.shape)} vs x {tuple(x.shape)}"
     frozen = (None if training
               else getattr(running_mean, "_cilfw_frozen", None))
     if frozen is not None:
         mean, invstd = frozen
         C = x.shape[-1]
+        assert C % 8 == 0, "bn kernels vectorize over channels (C%8==0)"
         M = x.numel() // C
         y = torch.empty_like(x)
         gf = gamma.float().contiguous()
@@ -431,6 +435,10 @@ def bn_bwd(dy, x, gamma, mean, invstd, y, relu, training, want_dres=False,
     bwd-data epilogue — the sums pass over (dy, x, y) is skipped."""
     _bf16(dy, "bn_bwd.dy")
     C = x.shape[-1]
+    assert C % 8 == 0, "bn kernels vectorize over channels (C%8==0)"
+    assert dy.shape == x.shape and y.shape == x.shape, \
+        f"bn_bwd: dy {tuple(dy.shape)} / y {tuple(y.shape)} vs x " \
+        f"{tuple(x.shape)}"
     M = x.numel() // C
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
@@ -461,6 +469,9 @@ def bn_bwd(dy, x, gamma, mean, invstd, y, relu, training, want_dres=False,
 
 def add_relu_fwd(a, b):
     _bf16(a, "add_relu.a")
+    _bf16(b, "add_relu.b")
+    assert a.shape == b.shape, \
+        f"add_relu: a {tuple(a.shape)} vs b {tuple(b.shape)}"
     y = torch.empty_like(a)
     _lib.cilfw_add_relu_fwd(_ptr(a), _ptr(b), _ptr(y), c_l(a.numel()),
                             _stream())
@@ -469,6 +480,9 @@ def add_relu_fwd(a, b):
 
 
 def add_relu_bwd(dy, y):
+    _bf16(dy, "add_relu_bwd.dy")
+    assert dy.shape == y.shape, \
+        f"add_relu_bwd: dy {tuple(dy.shape)} vs y {tuple(y.shape)}"
     da = torch.empty_like(dy)
     _lib.cilfw_add_relu_bwd(_ptr(dy), _ptr(y), _ptr(da), c_l(dy.numel()),
                             _stream())
@@ -479,7 +493,9 @@ def add_relu_bwd(dy, y):
 def downsample_a_fwd(x):
     _bf16(x, "downsample_a.x")
     N, H, W_, C = x.shape
-    y = torch.empty(N, H // 2, W_ // 2, 2 * C, dtype=x.dtype, device=x.device)
+    # AvgPool2d(1, 2) extent: the last row/column of an odd H/W is kept
+    y = torch.empty(N, (H + 1) // 2, (W_ + 1) // 2, 2 * C, dtype=x.dtype,
+                    device=x.device)
     _lib.cilfw_downsample_a_fwd(_ptr(x), _ptr(y), c_i(N), c_i(H), c_i(W_),
                                 c_i(C), _stream())
     _check("downsample_a_fwd")
@@ -487,8 +503,11 @@ def downsample_a_fwd(x):
 
 
 def downsample_a_bwd(dy, H, W_):
+    _bf16(dy, "downsample_a_bwd.dy")
     N = dy.shape[0]
     C = dy.shape[3] // 2
+    assert dy.shape == (N, (H + 1) // 2, (W_ + 1) // 2, 2 * C), \
+        f"downsample_a_bwd: dy {tuple(dy.shape)} for input {H}x{W_}"
     dx = torch.empty(N, H, W_, C, dtype=dy.dtype, device=dy.device)
     _lib.cilfw_downsample_a_bwd(_ptr(dy), _ptr(dx), c_i(N), c_i(H), c_i(W_),
                                 c_i(C), _stream())
@@ -507,6 +526,8 @@ def gap_fwd(x):
 
 
 def gap_bwd(dy, H, W_):
+    _bf16(dy, "gap_bwd.dy")
+    assert dy.dim() == 2, f"gap_bwd: dy {tuple(dy.shape)} is not (N, C)"
     N, C = dy.shape
     dx = torch.empty(N, H, W_, C, dtype=dy.dtype, device=dy.device)
     _lib.cilfw_gap_bwd(_ptr(dy), _ptr(dx), c_i(N), c_i(H * W_), c_i(C),
@@ -530,7 +551,13 @@ def maxpool_fwd(x, kernel, stride, pad):
 
 
 def maxpool_bwd(dy, idx, H, W_, kernel, stride, pad):
+    _bf16(dy, "maxpool_bwd.dy")
     N, Ho, Wo, C = dy.shape
+    assert (Ho, Wo) == _out_hw(H, W_, kernel, kernel, stride, pad) \
+        and idx.shape == dy.shape and idx.dtype == torch.int32 \
+        and idx.is_contiguous(), \
+        f"maxpool_bwd: dy {tuple(dy.shape)} / idx {tuple(idx.shape)} for " \
+        f"input {H}x{W_}"
     dx = torch.empty(N, H, W_, C, dtype=dy.dtype, device=dy.device)
     _lib.cilfw_maxpool_bwd(_ptr(dy), _ptr(idx), _ptr(dx), c_i(N), c_i(H),
                            c_i(W_), c_i(C), c_i(kernel), c_i(stride),

@@ -391,7 +391,8 @@ void add_relu_bwd_kernel(const bf16_t* __restrict__ dy,
 }
 
 // ---------------------------------------------------------------- DownsampleA
-// y (N,H/2,W/2,2C): [:, :, :, :C] = x[:, ::2, ::2, :], rest zero.
+// y (N,ceil(H/2),ceil(W/2),2C): [:, :, :, :C] = x[:, ::2, ::2, :], rest zero
+// (AvgPool2d(1, 2) keeps the last row/column of an odd extent).
 
 __global__ __launch_bounds__(NT)
 void downsample_a_fwd_kernel(const bf16_t* __restrict__ x,
@@ -399,7 +400,7 @@ void downsample_a_fwd_kernel(const bf16_t* __restrict__ x,
                              int C, long total_out) {
   long i = (long)blockIdx.x * NT + threadIdx.x;
   if (i >= total_out) return;
-  int C2 = 2 * C, Ho = H / 2, Wo = W / 2;
+  int C2 = 2 * C, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   int c = (int)(i % C2);
   long rest = i / C2;
   int wo = (int)(rest % Wo);
@@ -426,7 +427,7 @@ void downsample_a_bwd_kernel(const bf16_t* __restrict__ dy,
   int n = (int)(rest / H);
   bf16_t v = 0;
   if ((h & 1) == 0 && (w & 1) == 0) {
-    int Ho = H / 2, Wo = W / 2;
+    int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
     v = dy[(((long)n * Ho + h / 2) * Wo + w / 2) * (2 * C) + c];
   }
   dx[i] = v;
@@ -766,7 +767,7 @@ void cilfw_add_relu_bwd(const void* dy, const void* y, void* da, long total,
 
 void cilfw_downsample_a_fwd(const void* x, void* y, int N, int H, int W,
                             int C, void* stream) {
-  long total = (long)N * (H / 2) * (W / 2) * 2 * C;
+  long total = (long)N * ((H + 1) / 2) * ((W + 1) / 2) * 2 * C;
   hipLaunchKernelGGL(downsample_a_fwd_kernel,
                      dim3((int)cdiv((long)total, (long)NT)), dim3(NT), 0,
                      (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, N, H,

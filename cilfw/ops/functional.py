@@ -476,7 +476,8 @@ def add_relu(a, b):
 
 class DownsampleA(torch.autograd.Function):
     """Stride-2 1x1 avg-pool + zero-channel pad (reference resnet.py:9-17):
-    (N,H,W,C) -> (N,H/2,W/2,2C) where the second C channels are zeros."""
+    (N,H,W,C) -> (N,ceil(H/2),ceil(W/2),2C) where the second C channels are
+    zeros. AvgPool2d(1, 2) keeps the last row/column of an odd extent."""
 
     @staticmethod
     def forward(ctx, x):
@@ -484,7 +485,7 @@ class DownsampleA(torch.autograd.Function):
         if use_hip(x):
             return ext().downsample_a_fwd(x)
         N, H, W, C = x.shape
-        y = x.new_zeros(N, H // 2, W // 2, 2 * C)
+        y = x.new_zeros(N, (H + 1) // 2, (W + 1) // 2, 2 * C)
         y[:, :, :, :C] = x[:, ::2, ::2, :]
         return y
 

@@ -42,6 +42,20 @@ def test_resnet32_param_count():
     assert n == expected
 
 
+def test_resnet32_input_30_forward_backward():
+    """--input_size 30: the second downsample sees 15x15. The stride-2 conv
+    branch is 8x8, and so must the DownsampleA shortcut be (ceil extent, as
+    AvgPool2d(1, 2) gives it)."""
+    m = get_backbone("resnet32", 30)
+    x = torch.randn(2, 30, 30, 3, requires_grad=True)
+    f = m(x)
+    assert f.shape == (2, 64)
+    f.square().sum().backward()
+    assert x.grad.shape == x.shape and torch.isfinite(x.grad).all()
+    assert all(p.grad is not None and torch.isfinite(p.grad).all()
+               for p in m.parameters())
+
+
 def test_head_growth_and_forward():
     model = CilModel("resnet20", 32)
     model.prev_model_adaption(5)
