@@ -77,6 +77,8 @@ _PROTOS = {
     "cilfw_cos_sum": [c_vp] * 2 + [c_i, c_f, c_vp],
     "cilfw_flat_dist": [c_vp] * 5 + [c_i] * 2 + [c_vp],
     "cilfw_flat_bwd": [c_vp] * 3 + [c_i] * 2 + [c_vp],
+    "cilfw_mrank_fwd": [c_vp] * 9 + [c_i] * 4 + [c_f, c_vp],
+    "cilfw_mrank_bwd": [c_vp] * 6 + [c_i] * 4 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -86,7 +88,8 @@ for _name, _args in _PROTOS.items():
 _lib.cilfw_conv2d_bwd_data.restype = c_i  # 1 = BN partials were emitted
 for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd",
               "cilfw_rownorm_fwd", "cilfw_rownorm_bwd", "cilfw_cos_sum",
-              "cilfw_flat_dist", "cilfw_flat_bwd"):
+              "cilfw_flat_dist", "cilfw_flat_bwd", "cilfw_mrank_fwd",
+              "cilfw_mrank_bwd"):
     getattr(_lib, _name).restype = c_i  # 1 = shape refused, nothing launched
 
 for _name, _n in [("cilfw_linear_ksplit", 3),
@@ -102,7 +105,8 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_conv2d_bwd_weight_route", 8),
                   ("cilfw_pod_supported", 4),
                   ("cilfw_pod_pool_groups", 2),
-                  ("cilfw_cosine_supported", 3)]:
+                  ("cilfw_cosine_supported", 3),
+                  ("cilfw_mrank_supported", 4)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
@@ -1141,3 +1145,92 @@ def flat_bwd(gs, up, out=None):
     assert rc == 0, "flat_bwd: launcher refused the shape"
     _check("flat_bwd")
     return out
+
+
+# -------------------------------------------------------------- margin ranking
+
+def _mrank_args(M, C, known, k, name):
+    """The shape rule of csrc/mrank.hip (cilfw_mrank_supported)."""
+    known, k = int(known), int(k)
+    assert M >= 1 and C >= 2, \
+        f"{name}: needs M >= 1 rows and C >= 2 classes (got {M} x {C})"
+    assert 1 <= known < C, \
+        f"{name}: known must be in 1..C-1 (got known={known}, C={C})"
+    assert 1 <= k <= min(8, C - known), \
+        f"{name}: k must be in 1..min(8, C - known) (got k={k}, " \
+        f"C - known = {C - known})"
+    assert M * max(C, k) < 2 ** 62 and M < 2 ** 31 - 64 and C < 2 ** 31 - 64
+    assert _lib.cilfw_mrank_supported(M, C, known, k) == 1
+    return known, k
+
+
+def _mrank_buf(t, shape, dtype, ref, name):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=ref.device)
+    assert tuple(t.shape) == tuple(shape) and t.dtype == dtype \
+        and t.is_contiguous() and t.device == ref.device, \
+        f"{name}: out buffer must be a contiguous {dtype} tensor of shape " \
+        f"{tuple(shape)} on the device of the logits"
+    return t
+
+
+def mrank_fwd(logits, targets, sigma, known, k, margin, out=None):
+    """LUCIR's margin-ranking loss, forward (csrc/mrank.hip). logits (M, C)
+    bf16, targets (M,) int64, sigma: 1-element fp32 DEVICE tensor read by the
+    kernels (graph-safe). -> (loss 0-d fp32, sel int32 (M, k), fin fp32 (3,) =
+    [loss, q, dsigma for upstream 1], nold int32 (1,), rho fp32 (M,), dsum
+    fp32 (M,), old int32 (M,)). ``out``: a dict of buffers under those names
+    (every element of each is written)."""
+    assert logits.dim() == 2, "mrank_fwd: logits are (M, C)"
+    _bf16(logits, "mrank_fwd.logits")
+    M, C = logits.shape
+    known, k = _mrank_args(M, C, known, k, "mrank_fwd")
+    margin = float(margin)
+    assert margin >= 0.0, f"mrank_fwd: margin must be >= 0 (got {margin})"
+    assert targets.dtype == torch.int64 and targets.shape == (M,) \
+        and targets.is_contiguous() and targets.device == logits.device, \
+        "mrank_fwd: targets are a contiguous int64 (M,) tensor on the " \
+        "device of the logits"
+    sigma = _dev_scalar(sigma, logits, "mrank_fwd")
+    assert sigma is not None
+    out = out or {}
+    f32, i32 = torch.float32, torch.int32
+    sel = _mrank_buf(out.get("sel"), (M, k), i32, logits, "mrank_fwd.sel")
+    fin = _mrank_buf(out.get("fin"), (3,), f32, logits, "mrank_fwd.fin")
+    nold = _mrank_buf(out.get("nold"), (1,), i32, logits, "mrank_fwd.nold")
+    rho = _mrank_buf(out.get("rho"), (M,), f32, logits, "mrank_fwd.rho")
+    dsum = _mrank_buf(out.get("dsum"), (M,), f32, logits, "mrank_fwd.dsum")
+    old = _mrank_buf(out.get("old"), (M,), i32, logits, "mrank_fwd.old")
+    rc = _lib.cilfw_mrank_fwd(_ptr(logits), _ptr(targets), _ptr(sigma),
+                              _ptr(rho), _ptr(dsum), _ptr(old), _ptr(sel),
+                              _ptr(fin), _ptr(nold), c_i(M), c_i(C),
+                              c_i(known), c_i(k), c_f(margin), _stream())
+    assert rc == 0, "mrank_fwd: launcher refused the arguments"
+    _check("mrank_fwd")
+    return fin[0], sel, fin, nold, rho, dsum, old
+
+
+def mrank_bwd(sel, targets, fin, up, C, known, out=None, dsig=None):
+    """-> (dlogits bf16 (M, C), dsigma fp32 (1,)) from what mrank_fwd left:
+    +up q at the selected classes, -up q A at the target, 0 elsewhere (the
+    whole row is written). ``up``: 1-element fp32 DEVICE tensor (read by the
+    kernel: no host sync, graph-safe)."""
+    assert sel.dim() == 2 and sel.dtype == torch.int32 \
+        and sel.is_contiguous(), "mrank_bwd: sel is int32 (M, k)"
+    M, k = sel.shape
+    C = int(C)
+    known, k = _mrank_args(M, C, known, k, "mrank_bwd")
+    assert targets.dtype == torch.int64 and targets.shape == (M,) \
+        and targets.is_contiguous() and targets.device == sel.device
+    assert fin.shape == (3,) and fin.dtype == torch.float32 \
+        and fin.is_contiguous() and fin.device == sel.device
+    up = _dev_scalar(up, sel, "mrank_bwd")
+    assert up is not None
+    out = _mrank_buf(out, (M, C), torch.bfloat16, sel, "mrank_bwd.out")
+    dsig = _mrank_buf(dsig, (1,), torch.float32, sel, "mrank_bwd.dsig")
+    rc = _lib.cilfw_mrank_bwd(_ptr(sel), _ptr(targets), _ptr(fin), _ptr(up),
+                              _ptr(out), _ptr(dsig), c_i(M), c_i(C),
+                              c_i(known), c_i(k), _stream())
+    assert rc == 0, "mrank_bwd: launcher refused the arguments"
+    _check("mrank_bwd")
+    return out, dsig

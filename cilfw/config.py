@@ -99,6 +99,31 @@ def get_args_parser():
     parser.add_argument("--cos_scale_init", default=1.0, type=float,
                         help="initial value of the cosine head's trained "
                              "scale sigma (LUCIR starts at 1)")
+    parser.add_argument("--lambda_mr", default=0.0, type=float,
+                        help="weight of LUCIR's margin-ranking loss: each "
+                             "old-class sample's ground-truth cosine must "
+                             "beat its --mr_k hardest new-class cosines by "
+                             "--mr_margin; a mean over the old samples of "
+                             "the batch (under DDP: of each rank's batch, "
+                             "the per-rank count); constant weight, no sqrt "
+                             "factor; needs --head cosine (0 = off: no "
+                             "kernel of it runs; with --lambda_flat, "
+                             "--lambda_kd 0 and --imprint this is LUCIR)")
+    parser.add_argument("--mr_k", default=2, type=int,
+                        help="hard negatives per old sample of the "
+                             "margin-ranking loss (1..8, at most the number "
+                             "of new classes; LUCIR uses 2)")
+    parser.add_argument("--mr_margin", default=0.5, type=float,
+                        help="margin of the margin-ranking loss, on the "
+                             "cosines (>= 0; LUCIR uses 0.5)")
+    parser.add_argument("--imprint", action="store_true", default=False,
+                        help="LUCIR's class-mean imprinting: before each "
+                             "task after the first, set the new cosine "
+                             "head's weight rows to the normalised mean of "
+                             "the normalised features of their class, "
+                             "scaled to the mean norm of the old rows (one "
+                             "extra eval pass over the task set per task; "
+                             "needs --head cosine)")
 
     # ---- cilfw-native flags (no reference counterpart) ----
     parser.add_argument("--class_order", default=None, type=str,
@@ -167,6 +192,31 @@ def get_args_parser():
     return parser
 
 
+def check_args(args):
+    """Flag combinations refused at start-up (ValueError). Also called by
+    ``engine.run`` for a Namespace built without ``parse_args``."""
+    head = getattr(args, "head", "linear")
+    if getattr(args, "lambda_mr", 0.0) > 0 and head != "cosine":
+        raise ValueError(
+            f"--lambda_mr {args.lambda_mr} needs --head cosine (got --head "
+            f"{head}): the margin-ranking loss is defined on cosine logits")
+    if getattr(args, "imprint", False) and head != "cosine":
+        raise ValueError(
+            f"--imprint needs --head cosine (got --head {head}): only a "
+            f"cosine head's rows can be set to class means")
+    if getattr(args, "lambda_mr", 0.0) > 0:
+        if not 1 <= getattr(args, "mr_k", 2) <= 8:
+            raise ValueError(f"--mr_k must be in 1..8 (got {args.mr_k})")
+        if not getattr(args, "mr_margin", 0.5) >= 0:
+            raise ValueError(
+                f"--mr_margin must be >= 0 (got {args.mr_margin})")
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser("cilfw", parents=[get_args_parser()])
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    try:
+        check_args(args)
+    except ValueError as e:
+        parser.error(str(e))
+    return args

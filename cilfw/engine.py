@@ -202,6 +202,14 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
     if teacher is not None and getattr(args, "lambda_flat", 0.0) > 0:
         flat_w = args.lambda_flat * (known / args.increment_per_task) ** 0.5
     use_flat = flat_w > 0
+    # LUCIR's margin-ranking loss over the cosine logits (ops/margin.py), at
+    # a constant weight. Off: no kernel of the term is launched.
+    mr_w = 0.0
+    if teacher is not None and getattr(args, "lambda_mr", 0.0) > 0:
+        mr_w = args.lambda_mr
+    use_mr = mr_w > 0
+    mr_k = getattr(args, "mr_k", 2)
+    mr_margin = getattr(args, "mr_margin", 0.5)
 
     def teacher_fwd(inputs):
         """-> (t_logits, t_maps | None, t_features | None); the maps and the
@@ -246,11 +254,17 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
             loss_flat = ops.flat_loss(features, t_features)
             loss = loss + flat_w * loss_flat
             loss_flat = loss_flat.detach()
+        loss_mr = None
+        if use_mr:
+            loss_mr = ops.margin_rank_loss(logits, targets, model.fc.sigma,
+                                           known, mr_k, mr_margin)
+            loss = loss + mr_w * loss_mr
+            loss_mr = loss_mr.detach()
         loss.backward()
         engine.finalize()
         if update:
             optimizer.step()
-        return logits, loss_ce, loss_kd, loss, loss_pod, loss_flat
+        return logits, loss_ce, loss_kd, loss, loss_pod, loss_flat, loss_mr
 
     import os as _os
     can_graph = (str(device).startswith("cuda") and not args.no_step_graph
@@ -287,23 +301,23 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                 # logits refs keep AccumulateGrad nodes pinned to the default
                 # stream, which breaks (segfaults) stream capture.
                 logits = loss_ce = loss_kd = loss = loss_pod = None  # noqa: F841
-                loss_flat = None  # noqa: F841
+                loss_flat = loss_mr = None  # noqa: F841
                 try:
                     graphed = _GraphedStep(step_fn, inputs, targets, model)
                     (logits, loss_ce, loss_kd, loss, loss_pod,
-                     loss_flat) = graphed.out
+                     loss_flat, loss_mr) = graphed.out
                 except Exception as e:
                     print(f"[engine] step-graph capture failed "
                           f"({type(e).__name__}: {e}); running eager")
                     can_graph = False
                     (logits, loss_ce, loss_kd, loss, loss_pod,
-                     loss_flat) = step_fn(inputs, targets)
+                     loss_flat, loss_mr) = step_fn(inputs, targets)
             elif graphed is not None:
                 (logits, loss_ce, loss_kd, loss, loss_pod,
-                 loss_flat) = graphed(inputs, targets)
+                 loss_flat, loss_mr) = graphed(inputs, targets)
             else:
                 (logits, loss_ce, loss_kd, loss, loss_pod,
-                 loss_flat) = step_fn(inputs, targets)
+                 loss_flat, loss_mr) = step_fn(inputs, targets)
                 if args.compat_step_barrier:
                     barrier()  # reference per-step barrier (template.py:272)
             first_of_epoch = False
@@ -318,6 +332,8 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                     metric_logger.update(pod=loss_pod.item())
                 if loss_flat is not None:
                     metric_logger.update(flat=loss_flat.item())
+                if loss_mr is not None:
+                    metric_logger.update(mr=loss_mr.item())
                 metric_logger.update_n(n=bs, acc1=accs[0])
                 metric_logger.meters["lr"].update(optimizer.lr)
             step_i += 1
@@ -366,7 +382,40 @@ def extract_task_features(model, dataset, device, args, store=None):
     return torch.cat(feats)
 
 
+@torch.no_grad()
+def imprint_new_classes(model, dataset, device, args, store=None):
+    """LUCIR's class-mean imprinting (--imprint): one eval feature pass over
+    the task set, the unit-norm mean of the unit features of each new class
+    (ops.nme_prototypes), written into the newest cosine head scaled to the
+    mean norm of the old rows. Rows of classes < known (exemplars the host
+    replay path appended) are left out. Replicated on every rank, like
+    herding; consumes no random numbers."""
+    from .cil.nme import _torch_rng_kept
+    known = args.known_classes
+    with _torch_rng_kept():
+        feats = extract_task_features(model, dataset, device, args,
+                                      store=store)
+    labels = np.asarray(dataset.y).astype(np.int64).reshape(-1)
+    assert feats.shape[0] == labels.shape[0], \
+        f"feature pass yielded {feats.shape[0]} rows for {labels.shape[0]} " \
+        f"samples"
+    keep = np.nonzero(labels >= known)[0]
+    order = keep[np.argsort(labels[keep], kind="stable")]
+    nb_new = model.fc.heads[-1].out_features
+    assert order.size == 0 or labels[order[-1]] < known + nb_new, \
+        "task set holds labels beyond the new head's classes"
+    counts = np.bincount(labels[order] - known, minlength=nb_new)
+    seg_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rows = torch.from_numpy(order).to(feats.device)
+    protos = ops.nme_prototypes(feats[rows].contiguous(), seg_off)
+    n, norm_old = model.imprint_new_head(protos)
+    print(f"imprint: task {args.task_id}: {n} new head rows set to class "
+          f"means, mean old norm {norm_old:.4f}")
+
+
 def run(args):
+    from .config import check_args
+    check_args(args)
     init_distributed_mode(args)
     init_seed(args)
     device = args.device
@@ -515,6 +564,13 @@ def _run_tasks(args, device, watchdog):
                                     num_workers=args.workers)
 
         model.prev_model_adaption(args.increment_per_task)
+        if task_id > 0 and getattr(args, "imprint", False):
+            # before the engine and the optimizer flatten the parameters
+            imprint_store = None
+            if use_gpu_data and getattr(train_loader, "ragged", False):
+                imprint_store = train_loader.images[:train_loader.n_task]
+            imprint_new_classes(model, dataset_train, device, args,
+                                store=imprint_store)
         engine = DataParallelEngine(model, bucket_mb=args.ddp_bucket_mb)
         optimizer = FlatSGD(engine, args.lr, args.momentum, args.weight_decay)
         scheduler = CosineLR(optimizer, t_max=args.num_epochs)

@@ -235,6 +235,30 @@ class CilModel(nn.Module):
             self.weight_align(nb_classes)
 
     @torch.no_grad()
+    def imprint_new_head(self, protos):
+        """LUCIR's class-mean imprinting: ``protos (n_new, D)`` are the
+        unit-norm class prototypes of the newest head's classes in class
+        order (``ops.nme_prototypes``); its weight rows become ``p_c *
+        mean(|w_old rows|_2)``. -> (rows set, mean old norm)."""
+        if self.head_kind != "cosine":
+            raise RuntimeError(
+                "imprint_new_head: imprinting sets the rows of a cosine head "
+                f"(this model has a {self.head_kind} head)")
+        if self.fc is None or len(self.fc) < 2:
+            raise RuntimeError(
+                "imprint_new_head: needs at least one old head to take the "
+                "mean row norm from")
+        new = self.fc.heads[-1].weight
+        if protos.dim() != 2 or tuple(protos.shape) != tuple(new.shape):
+            raise ValueError(
+                f"imprint_new_head: {tuple(protos.shape)} prototypes for a "
+                f"new head of shape {tuple(new.shape)}")
+        w_old = torch.cat([h.weight for h in self.fc.heads[:-1]], dim=0)
+        norm_old = torch.norm(w_old.float(), p=2, dim=1).mean()
+        new.copy_((protos.to(new.device).float() * norm_old).to(new.dtype))
+        return new.shape[0], norm_old.item()
+
+    @torch.no_grad()
     def weight_align(self, nb_new_classes):
         """WA: rescale the newest head so mean new-row norm == mean old-row norm."""
         if self.head_kind == "cosine":

@@ -6,6 +6,7 @@ from .functional import (conv2d, batchnorm_act, batchnorm_add_relu, add_relu,
 from .nme import nme_prototypes, nme_topk
 from .pod import pod_pool, pod_spatial, pod_dist, pod_loss
 from .cosine import cosine_linear, flat_loss, flat_dist
+from .margin import margin_rank_loss, margin_rank_select
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
@@ -15,4 +16,5 @@ __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
            "crop_resize_ragged_reference", "nme_prototypes", "nme_topk",
            "pod_pool", "pod_spatial", "pod_dist", "pod_loss",
            "cosine_linear", "flat_loss", "flat_dist",
+           "margin_rank_loss", "margin_rank_select",
            "have_ext"]
