@@ -79,6 +79,10 @@ _PROTOS = {
     "cilfw_flat_bwd": [c_vp] * 3 + [c_i] * 2 + [c_vp],
     "cilfw_mrank_fwd": [c_vp] * 9 + [c_i] * 4 + [c_f, c_vp],
     "cilfw_mrank_bwd": [c_vp] * 6 + [c_i] * 4 + [c_vp],
+    "cilfw_lsc_reduce_fwd": [c_vp] * 4 + [c_i] * 3 + [c_f, c_vp],
+    "cilfw_lsc_reduce_bwd": [c_vp] * 6 + [c_i] * 3 + [c_f, c_vp],
+    "cilfw_nca_fwd": [c_vp] * 8 + [c_i] * 2 + [c_f, c_vp],
+    "cilfw_nca_bwd": [c_vp] * 8 + [c_i] * 2 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -89,7 +93,8 @@ _lib.cilfw_conv2d_bwd_data.restype = c_i  # 1 = BN partials were emitted
 for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd",
               "cilfw_rownorm_fwd", "cilfw_rownorm_bwd", "cilfw_cos_sum",
               "cilfw_flat_dist", "cilfw_flat_bwd", "cilfw_mrank_fwd",
-              "cilfw_mrank_bwd"):
+              "cilfw_mrank_bwd", "cilfw_lsc_reduce_fwd",
+              "cilfw_lsc_reduce_bwd", "cilfw_nca_fwd", "cilfw_nca_bwd"):
     getattr(_lib, _name).restype = c_i  # 1 = shape refused, nothing launched
 
 for _name, _n in [("cilfw_linear_ksplit", 3),
@@ -106,7 +111,9 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_pod_supported", 4),
                   ("cilfw_pod_pool_groups", 2),
                   ("cilfw_cosine_supported", 3),
-                  ("cilfw_mrank_supported", 4)]:
+                  ("cilfw_mrank_supported", 4),
+                  ("cilfw_lsc_supported", 3),
+                  ("cilfw_nca_supported", 2)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
@@ -1233,4 +1240,167 @@ def mrank_bwd(sel, targets, fin, up, C, known, out=None, dsig=None):
                               c_i(known), c_i(k), _stream())
     assert rc == 0, "mrank_bwd: launcher refused the arguments"
     _check("mrank_bwd")
+    return out, dsig
+
+
+# ------------------------------------------------------------------- LSC / NCA
+
+def _lsc_args(sims, nb_proxy, gamma, name):
+    """The shape rule of csrc/lsc.hip (cilfw_lsc_supported). -> M, C, K,
+    gamma."""
+    assert sims.dim() == 2, f"{name}: sims are (M, C * nb_proxy)"
+    assert sims.is_cuda, f"{name}: the kernels take GPU tensors (got a " \
+        f"host tensor)"
+    _bf16(sims, f"{name}.sims")
+    K, gamma = int(nb_proxy), float(gamma)
+    assert 1 <= K <= 16, f"{name}: nb_proxy must be in 1..16 (got {K})"
+    M, CK = sims.shape
+    assert M >= 1 and CK >= 1 and CK % K == 0, \
+        f"{name}: sims (M, C * nb_proxy) need M >= 1 and a column count " \
+        f"that is a multiple of nb_proxy = {K} (got {M} x {CK})"
+    assert gamma >= 0.0, f"{name}: gamma must be >= 0 (got {gamma})"
+    C = CK // K
+    assert M * CK < 2 ** 62 and M < 2 ** 31 - 64 and CK < 2 ** 31 - 64, \
+        f"{name}: sims too large for the kernels' int indices (got " \
+        f"{M} x {CK}; M and C * nb_proxy must stay below 2^31 - 64)"
+    assert _lib.cilfw_lsc_supported(M, C, K) == 1, \
+        f"{name}: cilfw_lsc_supported refuses (M, C, nb_proxy) = " \
+        f"({M}, {C}, {K})"
+    return M, C, K, gamma
+
+
+def _row_buf(t, shape, dtype, ref, name):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=ref.device)
+    assert tuple(t.shape) == tuple(shape) and t.dtype == dtype \
+        and t.is_contiguous() and t.device == ref.device, \
+        f"{name}: out buffer must be a contiguous {dtype} tensor of shape " \
+        f"{tuple(shape)} on the device of the input"
+    return t
+
+
+def lsc_reduce_fwd(sims, sigma, nb_proxy, gamma=1.0, out=None, yhat=None):
+    """PODNet's local similarity classifier, forward (csrc/lsc.hip). sims
+    (M, C * nb_proxy) bf16 cosines, class-major; sigma: 1-element fp32 DEVICE
+    tensor read by the kernel (graph-safe). -> (logits bf16 (M, C) = sigma
+    yhat, yhat fp32 (M, C)), yhat the softmax(gamma s)-weighted mean of each
+    class's cosines. ``out`` / ``yhat`` may be supplied (every element is
+    written)."""
+    M, C, K, gamma = _lsc_args(sims, nb_proxy, gamma, "lsc_reduce_fwd")
+    sigma = _dev_scalar(sigma, sims, "lsc_reduce_fwd")
+    assert sigma is not None, "lsc_reduce_fwd: sigma is required"
+    out = _row_buf(out, (M, C), torch.bfloat16, sims, "lsc_reduce_fwd.out")
+    yhat = _row_buf(yhat, (M, C), torch.float32, sims, "lsc_reduce_fwd.yhat")
+    rc = _lib.cilfw_lsc_reduce_fwd(_ptr(sims), _ptr(sigma), _ptr(out),
+                                   _ptr(yhat), c_i(M), c_i(C), c_i(K),
+                                   c_f(gamma), _stream())
+    assert rc == 0, "lsc_reduce_fwd: launcher refused the arguments"
+    _check("lsc_reduce_fwd")
+    return out, yhat
+
+
+def lsc_reduce_bwd(sims, yhat, g, sigma, nb_proxy, gamma=1.0, out=None,
+                   rows=None):
+    """-> (dsims bf16 (M, C * nb_proxy), rows fp32 (M,) = sum_c g_c yhat_c;
+    ``cos_sum(rows)`` is dsigma) from the sims, the yhat lsc_reduce_fwd left
+    and the upstream g bf16 (M, C). The softmax weights are recomputed."""
+    M, C, K, gamma = _lsc_args(sims, nb_proxy, gamma, "lsc_reduce_bwd")
+    assert yhat.shape == (M, C) and yhat.dtype == torch.float32 \
+        and yhat.is_contiguous() and yhat.device == sims.device, \
+        "lsc_reduce_bwd: yhat is the fp32 (M, C) tensor of lsc_reduce_fwd"
+    assert g.shape == (M, C) and g.device == sims.device, \
+        f"lsc_reduce_bwd: the upstream is (M, C) = ({M}, {C}) on the " \
+        f"device of the sims (got {tuple(g.shape)})"
+    _bf16(g, "lsc_reduce_bwd.g")
+    sigma = _dev_scalar(sigma, sims, "lsc_reduce_bwd")
+    assert sigma is not None, "lsc_reduce_bwd: sigma is required"
+    out = _row_buf(out, (M, C * K), torch.bfloat16, sims,
+                   "lsc_reduce_bwd.out")
+    rows = _row_buf(rows, (M,), torch.float32, sims, "lsc_reduce_bwd.rows")
+    rc = _lib.cilfw_lsc_reduce_bwd(_ptr(sims), _ptr(yhat), _ptr(g),
+                                   _ptr(sigma), _ptr(out), _ptr(rows),
+                                   c_i(M), c_i(C), c_i(K), c_f(gamma),
+                                   _stream())
+    assert rc == 0, "lsc_reduce_bwd: launcher refused the arguments"
+    _check("lsc_reduce_bwd")
+    return out, rows
+
+
+def _nca_args(logits, targets, name):
+    """The shape rule of csrc/lsc.hip (cilfw_nca_supported). -> M, C."""
+    assert logits.dim() == 2, f"{name}: logits are (M, C)"
+    assert logits.is_cuda, f"{name}: the kernels take GPU tensors (got a " \
+        f"host tensor)"
+    _bf16(logits, f"{name}.logits")
+    M, C = logits.shape
+    assert M >= 1 and C >= 2, \
+        f"{name}: needs M >= 1 rows and C >= 2 classes (got {M} x {C})"
+    assert targets.dtype == torch.int64 and targets.shape == (M,) \
+        and targets.is_contiguous() and targets.device == logits.device, \
+        f"{name}: targets are a contiguous int64 (M,) tensor on the " \
+        f"device of the logits"
+    assert M * C < 2 ** 62 and M < 2 ** 31 - 64 and C < 2 ** 31 - 64, \
+        f"{name}: logits too large for the kernels' int indices (got " \
+        f"{M} x {C}; M and C must stay below 2^31 - 64)"
+    assert _lib.cilfw_nca_supported(M, C) == 1, \
+        f"{name}: cilfw_nca_supported refuses (M, C) = ({M}, {C})"
+    return M, C
+
+
+def nca_fwd(logits, targets, sigma, margin, out=None):
+    """PODNet's NCA loss, forward (csrc/lsc.hip). logits (M, C) bf16, targets
+    (M,) int64, sigma: 1-element fp32 DEVICE tensor read by the kernels
+    (graph-safe). -> (loss 0-d fp32, h fp32 (M,), active int32 (M,), lse fp32
+    (M,), fin fp32 (3,) = [loss, 1/M, dsigma for upstream 1], nact int32
+    (1,)). ``out``: a dict of buffers under the names h, active, lse, fin,
+    nact (every element of each is written)."""
+    M, C = _nca_args(logits, targets, "nca_fwd")
+    margin = float(margin)
+    assert margin >= 0.0, f"nca_fwd: margin must be >= 0 (got {margin})"
+    sigma = _dev_scalar(sigma, logits, "nca_fwd")
+    assert sigma is not None, "nca_fwd: sigma is required"
+    out = out or {}
+    f32, i32 = torch.float32, torch.int32
+    h = _row_buf(out.get("h"), (M,), f32, logits, "nca_fwd.h")
+    lse = _row_buf(out.get("lse"), (M,), f32, logits, "nca_fwd.lse")
+    active = _row_buf(out.get("active"), (M,), i32, logits, "nca_fwd.active")
+    fin = _row_buf(out.get("fin"), (3,), f32, logits, "nca_fwd.fin")
+    nact = _row_buf(out.get("nact"), (1,), i32, logits, "nca_fwd.nact")
+    rc = _lib.cilfw_nca_fwd(_ptr(logits), _ptr(targets), _ptr(sigma), _ptr(h),
+                            _ptr(lse), _ptr(active), _ptr(fin), _ptr(nact),
+                            c_i(M), c_i(C), c_f(margin), _stream())
+    assert rc == 0, "nca_fwd: launcher refused the arguments"
+    _check("nca_fwd")
+    return fin[0], h, active, lse, fin, nact
+
+
+def nca_bwd(logits, targets, lse, active, fin, up, out=None, dsig=None):
+    """-> (dlogits bf16 (M, C), dsigma fp32 (1,)) from what nca_fwd left: the
+    softmax over the negatives times up/M and -up/M at the target for an
+    active row, 0 for every other row (the whole row is written). ``up``:
+    1-element fp32 DEVICE tensor (read by the kernel: no host sync,
+    graph-safe)."""
+    M, C = _nca_args(logits, targets, "nca_bwd")
+    f32 = torch.float32
+    assert lse.shape == (M,) and lse.dtype == f32 and lse.is_contiguous() \
+        and lse.device == logits.device, \
+        "nca_bwd: lse is the contiguous fp32 (M,) tensor of nca_fwd on the " \
+        "device of the logits"
+    assert active.shape == (M,) and active.dtype == torch.int32 \
+        and active.is_contiguous() and active.device == logits.device, \
+        "nca_bwd: active is the contiguous int32 (M,) tensor of nca_fwd on " \
+        "the device of the logits"
+    assert fin.shape == (3,) and fin.dtype == f32 and fin.is_contiguous() \
+        and fin.device == logits.device, \
+        "nca_bwd: fin is the contiguous fp32 (3,) tensor of nca_fwd on the " \
+        "device of the logits"
+    up = _dev_scalar(up, logits, "nca_bwd")
+    assert up is not None, "nca_bwd: the upstream scalar is required"
+    out = _row_buf(out, (M, C), torch.bfloat16, logits, "nca_bwd.out")
+    dsig = _row_buf(dsig, (1,), f32, logits, "nca_bwd.dsig")
+    rc = _lib.cilfw_nca_bwd(_ptr(logits), _ptr(targets), _ptr(lse),
+                            _ptr(active), _ptr(fin), _ptr(up), _ptr(out),
+                            _ptr(dsig), c_i(M), c_i(C), _stream())
+    assert rc == 0, "nca_bwd: launcher refused the arguments"
+    _check("nca_bwd")
     return out, dsig

@@ -44,6 +44,9 @@ def save_task_checkpoint(path_dir, task_id, model, memory, acc1s, args,
         if getattr(model, "head_kind", "linear") != "linear":
             # optional key: absent means a linear head
             state["head_kind"] = model.head_kind
+        if getattr(model, "nb_proxy", 1) != 1:
+            # optional key: absent means one proxy per class
+            state["nb_proxy"] = model.nb_proxy
         if getattr(args, "nme_eval", False):
             # optional key: absent from checkpoints written without the flag
             state["nme1s"] = list(getattr(args, "nme1s", []))
@@ -62,6 +65,12 @@ def load_task_checkpoint(path, model, memory, args, restore_rng=True):
         raise ValueError(
             f"checkpoint {path} was written with --head {saved_kind}; this "
             f"run uses --head {model_kind}")
+    saved_proxy = state.get("nb_proxy", 1)
+    model_proxy = getattr(model, "nb_proxy", 1)
+    if saved_proxy != model_proxy:
+        raise ValueError(
+            f"checkpoint {path} was written with --nb_proxy {saved_proxy}; "
+            f"this run uses --nb_proxy {model_proxy}")
     # grow the classifier to the checkpointed shape before loading weights
     for width in state["head_widths"]:
         model.prev_model_adaption(width)

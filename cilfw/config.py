@@ -124,6 +124,31 @@ def get_args_parser():
                              "scaled to the mean norm of the old rows (one "
                              "extra eval pass over the task set per task; "
                              "needs --head cosine)")
+    parser.add_argument("--nb_proxy", default=1, type=int,
+                        help="proxies per class of the cosine head (1..16): "
+                             "above 1 this is PODNet's local similarity "
+                             "classifier, each class's logit the "
+                             "softmax-weighted mean of its proxies' cosines "
+                             "(PODNet uses 10; needs --head cosine; 1 = the "
+                             "single-proxy head, no kernel of the reduce "
+                             "runs)")
+    parser.add_argument("--proxy_gamma", default=1.0, type=float,
+                        help="sharpness of the softmax over a class's "
+                             "proxies (>= 0; 0 = plain mean; PODNet uses 1; "
+                             "needs --head cosine)")
+    parser.add_argument("--cls_loss", default="ce", choices=["ce", "nca"],
+                        help="classification loss: cross entropy (with "
+                             "--lambda_kd logit distillation), or PODNet's "
+                             "NCA loss, a margin-softmax whose denominator "
+                             "leaves out the ground truth, hinged at 0 "
+                             "(needs --head cosine, --lambda_kd 0 and "
+                             "--smooth 0; with --nb_proxy 10, --lambda_pod "
+                             "and --lambda_flat this is PODNet; from "
+                             "--cos_scale_init 1 its margin term drives "
+                             "sigma below 0, see profiles/lsc_nca.md)")
+    parser.add_argument("--nca_margin", default=0.6, type=float,
+                        help="margin of the NCA loss, on the cosines (>= 0; "
+                             "PODNet uses 0.6)")
 
     # ---- cilfw-native flags (no reference counterpart) ----
     parser.add_argument("--class_order", default=None, type=str,
@@ -210,6 +235,46 @@ def check_args(args):
         if not getattr(args, "mr_margin", 0.5) >= 0:
             raise ValueError(
                 f"--mr_margin must be >= 0 (got {args.mr_margin})")
+    nb_proxy = getattr(args, "nb_proxy", 1)
+    gamma = getattr(args, "proxy_gamma", 1.0)
+    if not 1 <= nb_proxy <= 16:
+        raise ValueError(f"--nb_proxy must be in 1..16 (got {nb_proxy})")
+    if not gamma >= 0:
+        raise ValueError(f"--proxy_gamma must be >= 0 (got {gamma})")
+    if nb_proxy != 1 and head != "cosine":
+        raise ValueError(
+            f"--nb_proxy {nb_proxy} needs --head cosine (got --head {head}): "
+            f"the proxies are rows of a cosine head")
+    if gamma != 1.0 and head != "cosine":
+        raise ValueError(
+            f"--proxy_gamma {gamma} needs --head cosine (got --head {head}): "
+            f"it weights the proxies of a cosine head")
+    if getattr(args, "imprint", False) and nb_proxy > 1:
+        raise ValueError(
+            f"--imprint cannot be combined with --nb_proxy {nb_proxy}: "
+            f"identical proxies would never separate")
+    if getattr(args, "cls_loss", "ce") == "nca":
+        if head != "cosine":
+            raise ValueError(
+                f"--cls_loss nca needs --head cosine (got --head {head}): "
+                f"the NCA loss is defined on cosine logits")
+        if getattr(args, "lambda_kd", 0.0) != 0:
+            raise ValueError(
+                f"--cls_loss nca needs --lambda_kd 0 (got --lambda_kd "
+                f"{args.lambda_kd}): logit distillation is fused with the "
+                f"cross entropy")
+        if getattr(args, "dynamic_lambda_kd", False):
+            raise ValueError(
+                "--cls_loss nca cannot be combined with --dynamic_lambda_kd: "
+                "there is no logit distillation to weight")
+        if getattr(args, "smooth", 0.0) != 0:
+            raise ValueError(
+                f"--cls_loss nca needs --smooth 0 (got --smooth "
+                f"{args.smooth}): label smoothing belongs to the cross "
+                f"entropy")
+        if not getattr(args, "nca_margin", 0.6) >= 0:
+            raise ValueError(
+                f"--nca_margin must be >= 0 (got {args.nca_margin})")
 
 
 def parse_args(argv=None):

@@ -210,11 +210,25 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
     use_mr = mr_w > 0
     mr_k = getattr(args, "mr_k", 2)
     mr_margin = getattr(args, "mr_margin", 0.5)
+    # PODNet's NCA loss in place of CE + KD (ops/lsc.py); check_args has
+    # refused a non-zero lambda_kd or smooth with it
+    use_nca = getattr(args, "cls_loss", "ce") == "nca"
+    nca_margin = getattr(args, "nca_margin", 0.6)
 
     def teacher_fwd(inputs):
         """-> (t_logits, t_maps | None, t_features | None); the maps and the
         features stay referenced until the POD / flat term has read them,
-        like t_logits until wa_loss."""
+        like t_logits until wa_loss. With the NCA loss nothing reads the
+        teacher's logits, so its head is left out (for an LSC head: a
+        rownorm, the C K wide GEMM and the reduce per step) and the backbone
+        runs only for the terms that read its maps or features."""
+        if use_nca:
+            if use_pod:
+                t_feat, t_maps = teacher.backbone(inputs, return_maps=True)
+                return None, t_maps, (t_feat if use_flat else None)
+            if use_flat:
+                return None, None, teacher.extract_vector(inputs)
+            return None, None, None
         if use_pod:
             t_logits, t_feat, t_maps = teacher(inputs, return_maps=True)
             return t_logits, t_maps, (t_feat if use_flat else None)
@@ -237,6 +251,12 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
             else:
                 with torch.no_grad():
                     t_logits, t_maps, t_features = teacher_fwd(inputs)
+        loss_nca = None
+        if use_nca:
+            loss = ops.nca_loss(logits, targets, model.fc.sigma, nca_margin)
+            loss_ce = loss_kd = None
+            loss_nca = loss.detach()
+        elif teacher is not None:
             loss, loss_ce, loss_kd = ops.wa_loss(
                 logits, t_logits, targets, args.smooth,
                 args.kd_temperature, lambda_kd)
@@ -264,7 +284,8 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
         engine.finalize()
         if update:
             optimizer.step()
-        return logits, loss_ce, loss_kd, loss, loss_pod, loss_flat, loss_mr
+        return (logits, loss_ce, loss_kd, loss, loss_pod, loss_flat, loss_mr,
+                loss_nca)
 
     import os as _os
     can_graph = (str(device).startswith("cuda") and not args.no_step_graph
@@ -301,23 +322,23 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
                 # logits refs keep AccumulateGrad nodes pinned to the default
                 # stream, which breaks (segfaults) stream capture.
                 logits = loss_ce = loss_kd = loss = loss_pod = None  # noqa: F841
-                loss_flat = loss_mr = None  # noqa: F841
+                loss_flat = loss_mr = loss_nca = None  # noqa: F841
                 try:
                     graphed = _GraphedStep(step_fn, inputs, targets, model)
                     (logits, loss_ce, loss_kd, loss, loss_pod,
-                     loss_flat, loss_mr) = graphed.out
+                     loss_flat, loss_mr, loss_nca) = graphed.out
                 except Exception as e:
                     print(f"[engine] step-graph capture failed "
                           f"({type(e).__name__}: {e}); running eager")
                     can_graph = False
                     (logits, loss_ce, loss_kd, loss, loss_pod,
-                     loss_flat, loss_mr) = step_fn(inputs, targets)
+                     loss_flat, loss_mr, loss_nca) = step_fn(inputs, targets)
             elif graphed is not None:
                 (logits, loss_ce, loss_kd, loss, loss_pod,
-                 loss_flat, loss_mr) = graphed(inputs, targets)
+                 loss_flat, loss_mr, loss_nca) = graphed(inputs, targets)
             else:
                 (logits, loss_ce, loss_kd, loss, loss_pod,
-                 loss_flat, loss_mr) = step_fn(inputs, targets)
+                 loss_flat, loss_mr, loss_nca) = step_fn(inputs, targets)
                 if args.compat_step_barrier:
                     barrier()  # reference per-step barrier (template.py:272)
             first_of_epoch = False
@@ -326,8 +347,12 @@ def train_one_task(model, teacher, engine, optimizer, scheduler, train_loader,
             if step_i % metric_every == 0:  # host sync point (reads scalars)
                 accs = ops.accuracy(logits, targets,
                                     topk=(1, min(5, logits.shape[1])))
-                metric_logger.update(ce=loss_ce.item(), kd=loss_kd.item(),
-                                     loss=loss.item())
+                if loss_nca is not None:
+                    metric_logger.update(nca=loss_nca.item(),
+                                         loss=loss.item())
+                else:
+                    metric_logger.update(ce=loss_ce.item(),
+                                         kd=loss_kd.item(), loss=loss.item())
                 if loss_pod is not None:
                     metric_logger.update(pod=loss_pod.item())
                 if loss_flat is not None:
@@ -456,7 +481,9 @@ def _run_tasks(args, device, watchdog):
 
     model = CilModel(args.backbone, args.input_size,
                      head=getattr(args, "head", "linear"),
-                     cos_scale_init=getattr(args, "cos_scale_init", 1.0)
+                     cos_scale_init=getattr(args, "cos_scale_init", 1.0),
+                     nb_proxy=getattr(args, "nb_proxy", 1),
+                     proxy_gamma=getattr(args, "proxy_gamma", 1.0)
                      ).to(device)
     barrier()
 

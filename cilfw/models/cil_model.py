@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from ..ops import functional as CF
 from ..ops import cosine as COS
+from ..ops import lsc as LSC
 from . import resnet_cifar, resnet
 
 
@@ -86,18 +87,38 @@ class CosineClassifier(nn.Module):
     one proxy per class): logits = sigma * cos(feature, class weight), heads
     concatenated in head order. No bias; ONE scale ``sigma`` shared by all
     heads and trained like any other parameter. Rescaling a weight row cannot
-    change a logit, so no weight alignment applies."""
+    change a logit, so no weight alignment applies.
 
-    def __init__(self, embed_dim, nb_classes, scale_init=1.0):
+    ``nb_proxy = K > 1`` is PODNet's full LSC head: a head for ``n`` classes
+    holds ``weight (n K, D)``, class-major (class ``c``'s proxies are rows
+    ``c K .. c K + K - 1``), ``out_features`` stays ``n``, and the ``K``
+    cosines of a class are reduced by ``ops.lsc_reduce`` (their
+    softmax(``proxy_gamma`` cosine)-weighted mean, times ``sigma``)."""
+
+    def __init__(self, embed_dim, nb_classes, scale_init=1.0, nb_proxy=1,
+                 proxy_gamma=1.0):
         super().__init__()
+        if not 1 <= int(nb_proxy) <= LSC.MAX_PROXY:
+            raise ValueError(f"nb_proxy must be in 1..{LSC.MAX_PROXY} "
+                             f"(got {nb_proxy})")
+        if not float(proxy_gamma) >= 0:
+            raise ValueError(f"proxy_gamma must be >= 0 (got {proxy_gamma})")
         self.embed_dim = embed_dim
+        self.nb_proxy = int(nb_proxy)
+        self.proxy_gamma = float(proxy_gamma)
         self.heads = nn.ModuleList()
         self.sigma = nn.Parameter(torch.full((1,), float(scale_init)))
+        if self.nb_proxy > 1:
+            # the scale of the pure cosines that lsc_reduce reads: not
+            # trained, not part of the state dict
+            self.register_buffer("unit_scale", torch.ones(1),
+                                 persistent=False)
         self.adaption(nb_classes)
 
     def adaption(self, nb_new_classes):
         head = nn.Module()
-        head.weight = nn.Parameter(torch.empty(nb_new_classes, self.embed_dim))
+        head.weight = nn.Parameter(torch.empty(
+            nb_new_classes * self.nb_proxy, self.embed_dim))
         nn.init.kaiming_normal_(head.weight)
         head.out_features = nb_new_classes
         self.heads.append(head)
@@ -110,6 +131,17 @@ class CosineClassifier(nn.Module):
         # one cosine_linear over the row-concatenated fp32 masters; a frozen
         # model uses its cached normalised rows (cast_compute_weights_)
         cat = getattr(self, "_frozen_cat", None)
+        if self.nb_proxy > 1:
+            # pure cosines against all n K proxies, then the per-class reduce
+            if cat is not None:
+                with torch.no_grad():
+                    sims = COS.cosine_linear_frozen(x, cat[0], cat[2])
+                    return LSC.lsc_reduce(sims, cat[1], self.nb_proxy,
+                                          self.proxy_gamma)
+            w = torch.cat([h.weight for h in self.heads], dim=0)
+            sims = COS.cosine_linear(x, w, self.unit_scale)
+            return LSC.lsc_reduce(sims, self.sigma, self.nb_proxy,
+                                  self.proxy_gamma)
         if cat is not None:
             return COS.cosine_linear_frozen(x, cat[0], cat[1])
         w = torch.cat([h.weight for h in self.heads], dim=0)
@@ -127,11 +159,16 @@ HEAD_KINDS = ("linear", "cosine")
 
 class CilModel(nn.Module):
     def __init__(self, backbone_name, input_size=32, head="linear",
-                 cos_scale_init=1.0):
+                 cos_scale_init=1.0, nb_proxy=1, proxy_gamma=1.0):
         super().__init__()
         if head not in HEAD_KINDS:
             raise ValueError(f"unknown head kind {head!r} (one of "
                              f"{HEAD_KINDS})")
+        if int(nb_proxy) != 1 and head != "cosine":
+            raise ValueError(f"nb_proxy = {nb_proxy} needs a cosine head "
+                             f"(got head {head!r})")
+        self.nb_proxy = int(nb_proxy)
+        self.proxy_gamma = float(proxy_gamma)
         self.backbone = get_backbone(backbone_name, input_size)
         self.head_kind = head
         self.cos_scale_init = cos_scale_init
@@ -202,6 +239,9 @@ class CilModel(nn.Module):
             self.fc._frozen_cat = (
                 COS.cosine_normalize_weights(w).to(dtype).contiguous(),
                 self.fc.sigma.detach().float().clone())
+            if self.fc.nb_proxy > 1:
+                self.fc._frozen_cat += (
+                    self.fc.unit_scale.detach().float().clone(),)
         elif self.fc is not None:
             for h in self.fc.heads:
                 h.weight.data = h.weight.data.to(dtype)
@@ -215,7 +255,8 @@ class CilModel(nn.Module):
         if self.fc is None:
             if self.head_kind == "cosine":
                 self.fc = CosineClassifier(self.feature_dim, nb_classes,
-                                           self.cos_scale_init)
+                                           self.cos_scale_init,
+                                           self.nb_proxy, self.proxy_gamma)
             else:
                 self.fc = CilClassifier(self.feature_dim, nb_classes)
         else:
@@ -248,6 +289,10 @@ class CilModel(nn.Module):
             raise RuntimeError(
                 "imprint_new_head: needs at least one old head to take the "
                 "mean row norm from")
+        if self.fc.nb_proxy > 1:
+            raise RuntimeError(
+                "imprint_new_head: a head with nb_proxy > 1 cannot be "
+                "imprinted (identical proxies would never separate)")
         new = self.fc.heads[-1].weight
         if protos.dim() != 2 or tuple(protos.shape) != tuple(new.shape):
             raise ValueError(
