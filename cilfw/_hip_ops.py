@@ -14,6 +14,8 @@ import os
 
 import torch
 
+from . import _herding_checks as _hc
+
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                          "_hip_lib.so")
 if not os.path.exists(_LIB_PATH):
@@ -830,9 +832,18 @@ def crop_resize_ragged(pool, offsets, hw, channels, idx, params, flip,
 
 
 def herding_select(f, mu, m):
-    n, D = f.shape
-    assert (n + D) * 4 <= 60_000, \
+    """Greedy herding of one class: f (n, D) fp32 contiguous GPU features, mu
+    (D,) their mean, 0 <= m <= n -> (m,) int64 ranked indices. Bad arguments
+    and non-finite / oversized values raise ValueError before any launch
+    (``_herding_checks``: with them no candidate would win a step and the
+    kernel would index out of bounds)."""
+    n, D, m = _hc.check_select_args(f, mu, m)
+    if not f.is_cuda:
+        raise ValueError("herding_select: features must be on the GPU")
+    assert (n + D) * 4 <= _hc.LDS_BYTES, \
         "herding_select kernel supports n+D <= 15000 (per-class sample sets)"
+    # one reduction + one sync per call; herding runs once per task
+    _hc.check_values("herding_select", f, mu)
     order = torch.empty(m, dtype=torch.int64, device=f.device)
     _lib.cilfw_herding_select(_ptr(f), _ptr(mu), _ptr(order), c_i(n), c_i(D),
                               c_i(m), _stream())
@@ -843,12 +854,17 @@ def herding_select(f, mu, m):
 def herding_select_batch(feats_list, m_list):
     """All classes' greedy herding in ONE launch (block per class).
     feats_list: list of (n_c, D) fp32 GPU tensors; returns list of int64
-    ranked-index tensors (local indices, length m_c)."""
-    device = feats_list[0].device
-    D = feats_list[0].shape[1]
-    ns = [int(f.shape[0]) for f in feats_list]
-    assert all((n + D) * 4 <= 60_000 for n in ns), "herding LDS limit"
+    ranked-index tensors (local indices, length m_c = min(m, n_c)). A list
+    whose entries disagree in D or device, a quota list of another length and
+    non-finite / oversized values raise ValueError before any launch; the
+    message names the position of the offending class."""
+    ns, D, device = _hc.check_batch_args(feats_list, m_list)
+    if device.type != "cuda":
+        raise ValueError("herding_select_batch: features must be on the GPU")
+    assert all((n + D) * 4 <= _hc.LDS_BYTES for n in ns), "herding LDS limit"
     fall = torch.cat([f.float().contiguous() for f in feats_list])
+    # one reduction + one sync per call; herding runs once per task
+    _hc.check_values_batch(fall, ns, "herding_select_batch")
     mus = torch.stack([f.float().mean(0) for f in feats_list]).contiguous()
     foff = torch.tensor([0] + list(torch.tensor(ns).cumsum(0)),
                         dtype=torch.int32, device=device)

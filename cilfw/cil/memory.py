@@ -17,6 +17,7 @@ candidate-distance scan; torch ops on CPU).
 import numpy as np
 import torch
 
+from .._herding_checks import check_values
 from ..ops._backend import use_hip, ext
 
 
@@ -25,13 +26,20 @@ def herding_select(features, m):
 
     features: (n, D) float tensor (any device). Deterministic; ties break to the
     lowest index (torch.argmin semantics), replicated identically on every rank.
+
+    Non-finite features, or max|f| > 2^48 (where the fp32 distances could
+    overflow), raise ValueError on either device: no candidate would win a
+    step (``_herding_checks``). That costs one reduction and one sync per
+    call; herding runs once per task.
     """
     f = features.float()
     n = f.shape[0]
     m = min(m, n)
     mu = f.mean(dim=0)
     if f.is_cuda and use_hip(f):
+        # the wrapper refuses bad values itself, before its launch
         return ext().herding_select(f.contiguous(), mu.contiguous(), m)
+    check_values("herding_select", f)
     selected = torch.zeros(n, dtype=torch.bool, device=f.device)
     sum_sel = torch.zeros_like(mu)
     order = torch.empty(m, dtype=torch.int64, device=f.device)
