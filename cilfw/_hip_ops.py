@@ -85,6 +85,7 @@ _PROTOS = {
     "cilfw_lsc_reduce_bwd": [c_vp] * 6 + [c_i] * 3 + [c_f, c_vp],
     "cilfw_nca_fwd": [c_vp] * 8 + [c_i] * 2 + [c_f, c_vp],
     "cilfw_nca_bwd": [c_vp] * 8 + [c_i] * 2 + [c_vp],
+    "cilfw_kmeans_proxies": [c_vp] * 8 + [c_i] * 5 + [c_vp],
 }
 for _name, _args in _PROTOS.items():
     _fn = getattr(_lib, _name)
@@ -96,7 +97,8 @@ for _name in ("cilfw_pod_pool", "cilfw_pod_dist", "cilfw_pod_bwd",
               "cilfw_rownorm_fwd", "cilfw_rownorm_bwd", "cilfw_cos_sum",
               "cilfw_flat_dist", "cilfw_flat_bwd", "cilfw_mrank_fwd",
               "cilfw_mrank_bwd", "cilfw_lsc_reduce_fwd",
-              "cilfw_lsc_reduce_bwd", "cilfw_nca_fwd", "cilfw_nca_bwd"):
+              "cilfw_lsc_reduce_bwd", "cilfw_nca_fwd", "cilfw_nca_bwd",
+              "cilfw_kmeans_proxies"):
     getattr(_lib, _name).restype = c_i  # 1 = shape refused, nothing launched
 
 for _name, _n in [("cilfw_linear_ksplit", 3),
@@ -115,7 +117,8 @@ for _name, _n in [("cilfw_linear_ksplit", 3),
                   ("cilfw_cosine_supported", 3),
                   ("cilfw_mrank_supported", 4),
                   ("cilfw_lsc_supported", 3),
-                  ("cilfw_nca_supported", 2)]:
+                  ("cilfw_nca_supported", 2),
+                  ("cilfw_kmeans_supported", 3)]:
     _fn = getattr(_lib, _name)
     _fn.argtypes = [c_i] * _n
     _fn.restype = c_i
@@ -944,6 +947,98 @@ def nme_topk(feats, protos, maxk, targets=None):
                         c_i(maxk), _stream())
     _check("nme_topk")
     return idx, score, counts
+
+
+# ---------------------------------------------------------------------- kmeans
+
+KMEANS_MAX_ABS = 2.0 ** 48
+
+
+def kmeans_proxies(feats, seg_off, K, max_iter, out=None):
+    """K-means proxies of every class in ONE launch (csrc/kmeans.hip: maximin
+    seeding and Lloyd iterations, block per class). feats fp32 (n, D)
+    contiguous GPU rows grouped by class; seg_off int32 (C+1,) device tensor of
+    row offsets. -> (proxies fp32 (C*K, D) unit rows, class-major; assign
+    int32 (n,) class-local centre of every row; iters int32 (C,)). ``out``:
+    that triple supplied by the caller (every element is written).
+
+    Bad arguments, a shape ``cilfw_kmeans_supported`` refuses, a class with
+    fewer than K rows and non-finite / oversized values raise ValueError
+    before any launch: a NaN distance wins no ``<`` (the defect found in
+    herding), and with max|f| <= 2^48 no row norm overflows (D <= 4096:
+    |f|^2 <= 2^108). Two host syncs per call (offsets, values); the op runs
+    once per task."""
+    what = "kmeans_proxies"
+    if not (torch.is_tensor(feats) and feats.dim() == 2):
+        raise ValueError(f"{what}: features must be a 2-d tensor (n, D)")
+    if feats.dtype != torch.float32:
+        raise ValueError(f"{what}: features must be fp32 (got {feats.dtype})")
+    if not feats.is_contiguous():
+        raise ValueError(f"{what}: features must be contiguous")
+    if not feats.is_cuda:
+        raise ValueError(f"{what}: features must be on the GPU")
+    if not (torch.is_tensor(seg_off) and seg_off.dtype == torch.int32
+            and seg_off.dim() == 1 and seg_off.numel() >= 2
+            and seg_off.is_contiguous() and seg_off.device == feats.device):
+        raise ValueError(
+            f"{what}: seg_off must be a contiguous int32 (C+1,) tensor on the "
+            f"device of the features")
+    n, D = feats.shape
+    K, max_iter = int(K), int(max_iter)
+    if max_iter < 1:
+        raise ValueError(f"{what}: max_iter must be >= 1 (got {max_iter})")
+    off = seg_off.cpu().tolist()
+    if off[0] != 0 or off[-1] != n or any(b < a for a, b in
+                                           zip(off[:-1], off[1:])):
+        raise ValueError(
+            f"{what}: seg_off must run from 0 to n = {n} without decreasing "
+            f"(got {off})")
+    sizes = [b - a for a, b in zip(off[:-1], off[1:])]
+    small = [c for c, q in enumerate(sizes) if q < K]
+    if small and 1 <= K <= 16:
+        raise ValueError(
+            f"{what}: class segment(s) {small} hold fewer than K = {K} rows")
+    if _lib.cilfw_kmeans_supported(c_i(min(sizes)), c_i(D), c_i(K)) != 1:
+        raise ValueError(
+            f"{what}: cilfw_kmeans_supported refuses (n_min, D, K) = "
+            f"({min(sizes)}, {D}, {K}): needs D % 4 == 0, 4 <= D <= 4096, "
+            f"1 <= K <= 16, K * D <= 16000 (the centres live in LDS) and "
+            f"n >= K")
+    if n * D >= 2 ** 40:
+        raise ValueError(f"{what}: {n} x {D} features are too many")
+    a = feats.detach().abs().amax().item()
+    if not (a <= KMEANS_MAX_ABS):  # written so that NaN fails
+        raise ValueError(
+            f"{what}: features must be finite with max|f| <= 2^48 (got "
+            f"max|f| = {a}); a diverged run cannot be clustered")
+    assert feats.data_ptr() % 16 == 0  # the kernel loads 16-byte vectors
+    C, dev = len(sizes), feats.device
+    xh = torch.empty(n, D, dtype=torch.float32, device=dev)
+    xx = torch.empty(n, dtype=torch.float32, device=dev)
+    dmin = torch.empty(n, dtype=torch.float32, device=dev)
+    if out is None:
+        out = (torch.empty(C * K, D, dtype=torch.float32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(C, dtype=torch.int32, device=dev))
+    proxies, assign, iters = out
+    for t, shape, dt in ((proxies, (C * K, D), torch.float32),
+                         (assign, (n,), torch.int32),
+                         (iters, (C,), torch.int32)):
+        if not (tuple(t.shape) == shape and t.dtype == dt
+                and t.is_contiguous() and t.device == dev):
+            raise ValueError(
+                f"{what}: out must hold contiguous proxies ({C * K}, {D}) "
+                f"fp32, assign ({n},) int32 and iters ({C},) int32 on the "
+                f"device of the features")
+    rc = _lib.cilfw_kmeans_proxies(_ptr(feats), _ptr(seg_off), _ptr(xh),
+                                   _ptr(xx), _ptr(dmin), _ptr(proxies),
+                                   _ptr(assign), _ptr(iters), c_i(C),
+                                   c_i(min(sizes)), c_i(D), c_i(K),
+                                   c_i(max_iter), _stream())
+    if rc != 0:
+        raise RuntimeError(f"{what}: launcher refused the shape")
+    _check(what)
+    return proxies, assign, iters
 
 
 # ------------------------------------------------------------------------- pod

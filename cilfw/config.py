@@ -132,6 +132,20 @@ def get_args_parser():
                              "(PODNet uses 10; needs --head cosine; 1 = the "
                              "single-proxy head, no kernel of the reduce "
                              "runs)")
+    parser.add_argument("--proxy_init", default="random",
+                        choices=["random", "kmeans"],
+                        help="start of each new task's proxies: the head's "
+                             "random init, or PODNet's k-means: the K "
+                             "proxies of a new class start at the K k-means "
+                             "centres of its normalised features, scaled to "
+                             "the mean norm of the old rows (one extra eval "
+                             "pass over the task set and one kernel launch "
+                             "per task; needs --head cosine and --nb_proxy "
+                             "> 1; random = no kernel of it runs)")
+    parser.add_argument("--kmeans_iters", default=100, type=int,
+                        help="most Lloyd iterations of --proxy_init kmeans "
+                             "(>= 1; it stops earlier once no assignment "
+                             "changes)")
     parser.add_argument("--proxy_gamma", default=1.0, type=float,
                         help="sharpness of the softmax over a class's "
                              "proxies (>= 0; 0 = plain mean; PODNet uses 1; "
@@ -253,6 +267,18 @@ def check_args(args):
         raise ValueError(
             f"--imprint cannot be combined with --nb_proxy {nb_proxy}: "
             f"identical proxies would never separate")
+    if getattr(args, "proxy_init", "random") == "kmeans":
+        if head != "cosine":
+            raise ValueError(
+                f"--proxy_init kmeans needs --head cosine (got --head "
+                f"{head}): the proxies are rows of a cosine head")
+        if nb_proxy == 1:
+            raise ValueError(
+                "--proxy_init kmeans needs --nb_proxy > 1: a single proxy "
+                "per class is set to the class mean with --imprint")
+        if not getattr(args, "kmeans_iters", 100) >= 1:
+            raise ValueError(
+                f"--kmeans_iters must be >= 1 (got {args.kmeans_iters})")
     if getattr(args, "cls_loss", "ce") == "nca":
         if head != "cosine":
             raise ValueError(

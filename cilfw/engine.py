@@ -408,13 +408,11 @@ def extract_task_features(model, dataset, device, args, store=None):
 
 
 @torch.no_grad()
-def imprint_new_classes(model, dataset, device, args, store=None):
-    """LUCIR's class-mean imprinting (--imprint): one eval feature pass over
-    the task set, the unit-norm mean of the unit features of each new class
-    (ops.nme_prototypes), written into the newest cosine head scaled to the
-    mean norm of the old rows. Rows of classes < known (exemplars the host
-    replay path appended) are left out. Replicated on every rank, like
-    herding; consumes no random numbers."""
+def _new_class_features(model, dataset, device, args, store=None):
+    """One eval feature pass over the task set -> (features of the new
+    classes' rows sorted by label (stable), seg_off (nb_new + 1,) int64 row
+    offsets of the class segments). Rows of classes < known (exemplars the
+    host replay path appended) are left out. Consumes no random numbers."""
     from .cil.nme import _torch_rng_kept
     known = args.known_classes
     with _torch_rng_kept():
@@ -432,10 +430,44 @@ def imprint_new_classes(model, dataset, device, args, store=None):
     counts = np.bincount(labels[order] - known, minlength=nb_new)
     seg_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     rows = torch.from_numpy(order).to(feats.device)
-    protos = ops.nme_prototypes(feats[rows].contiguous(), seg_off)
+    return feats[rows].contiguous(), seg_off
+
+
+@torch.no_grad()
+def imprint_new_classes(model, dataset, device, args, store=None):
+    """LUCIR's class-mean imprinting (--imprint): one eval feature pass over
+    the task set, the unit-norm mean of the unit features of each new class
+    (ops.nme_prototypes), written into the newest cosine head scaled to the
+    mean norm of the old rows. Rows of classes < known (exemplars the host
+    replay path appended) are left out. Replicated on every rank, like
+    herding; consumes no random numbers."""
+    feats, seg_off = _new_class_features(model, dataset, device, args,
+                                         store=store)
+    protos = ops.nme_prototypes(feats, seg_off)
     n, norm_old = model.imprint_new_head(protos)
     print(f"imprint: task {args.task_id}: {n} new head rows set to class "
           f"means, mean old norm {norm_old:.4f}")
+
+
+@torch.no_grad()
+def init_new_proxies_kmeans(model, dataset, device, args, store=None):
+    """PODNet's proxy initialisation (--proxy_init kmeans): one eval feature
+    pass over the task set, the K = --nb_proxy k-means centres of the unit
+    features of each new class (ops.kmeans_proxies: one launch for all
+    classes), written into the newest head scaled to the mean norm of the old
+    rows. Replicated on every rank; deterministic and free of random numbers,
+    so the ranks agree bit for bit."""
+    from .cil.nme import _torch_rng_kept
+    with _torch_rng_kept():
+        feats, seg_off = _new_class_features(model, dataset, device, args,
+                                             store=store)
+        proxies, _assign, iters = ops.kmeans_proxies(
+            feats, seg_off, model.fc.nb_proxy,
+            max_iter=getattr(args, "kmeans_iters", 100))
+        n, norm_old = model.init_new_proxies(proxies)
+    print(f"proxy init: task {args.task_id}: {n} new head rows set to k-means "
+          f"centres, mean old norm {norm_old:.4f}, iterations "
+          f"{int(iters.min())}..{int(iters.max())}")
 
 
 def run(args):
@@ -598,6 +630,13 @@ def _run_tasks(args, device, watchdog):
                 imprint_store = train_loader.images[:train_loader.n_task]
             imprint_new_classes(model, dataset_train, device, args,
                                 store=imprint_store)
+        if task_id > 0 and getattr(args, "proxy_init", "random") == "kmeans":
+            # before the engine and the optimizer flatten the parameters
+            proxy_store = None
+            if use_gpu_data and getattr(train_loader, "ragged", False):
+                proxy_store = train_loader.images[:train_loader.n_task]
+            init_new_proxies_kmeans(model, dataset_train, device, args,
+                                    store=proxy_store)
         engine = DataParallelEngine(model, bucket_mb=args.ddp_bucket_mb)
         optimizer = FlatSGD(engine, args.lr, args.momentum, args.weight_decay)
         scheduler = CosineLR(optimizer, t_max=args.num_epochs)

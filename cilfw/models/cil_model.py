@@ -304,6 +304,36 @@ class CilModel(nn.Module):
         return new.shape[0], norm_old.item()
 
     @torch.no_grad()
+    def init_new_proxies(self, proxies):
+        """PODNet's k-means initialisation of a multi-proxy head: ``proxies
+        (n_new * nb_proxy, D)`` are the unit-norm k-means centres of the
+        newest head's classes, class-major (``ops.kmeans_proxies``); its
+        weight rows become ``proxies * mean(|w_old rows|_2)``. -> (rows set,
+        mean old norm)."""
+        if self.head_kind != "cosine":
+            raise RuntimeError(
+                "init_new_proxies: proxies are the rows of a cosine head "
+                f"(this model has a {self.head_kind} head)")
+        if self.fc is None or len(self.fc) < 2:
+            raise RuntimeError(
+                "init_new_proxies: needs at least one old head to take the "
+                "mean row norm from")
+        if self.fc.nb_proxy == 1:
+            raise RuntimeError(
+                "init_new_proxies: a head with nb_proxy = 1 has one row per "
+                "class; set it to the class mean with imprint_new_head")
+        new = self.fc.heads[-1].weight
+        if proxies.dim() != 2 or tuple(proxies.shape) != tuple(new.shape):
+            raise ValueError(
+                f"init_new_proxies: {tuple(proxies.shape)} proxies for a "
+                f"new head of shape {tuple(new.shape)} (classes x nb_proxy = "
+                f"{self.fc.nb_proxy} rows)")
+        w_old = torch.cat([h.weight for h in self.fc.heads[:-1]], dim=0)
+        norm_old = torch.norm(w_old.float(), p=2, dim=1).mean()
+        new.copy_((proxies.to(new.device).float() * norm_old).to(new.dtype))
+        return new.shape[0], norm_old.item()
+
+    @torch.no_grad()
     def weight_align(self, nb_new_classes):
         """WA: rescale the newest head so mean new-row norm == mean old-row norm."""
         if self.head_kind == "cosine":

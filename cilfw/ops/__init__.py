@@ -8,6 +8,7 @@ from .pod import pod_pool, pod_spatial, pod_dist, pod_loss
 from .cosine import cosine_linear, flat_loss, flat_dist
 from .margin import margin_rank_loss, margin_rank_select
 from .lsc import lsc_reduce, nca_loss, nca_rows
+from .kmeans import kmeans_proxies
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
@@ -18,5 +19,5 @@ __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
            "pod_pool", "pod_spatial", "pod_dist", "pod_loss",
            "cosine_linear", "flat_loss", "flat_dist",
            "margin_rank_loss", "margin_rank_select",
-           "lsc_reduce", "nca_loss", "nca_rows",
+           "lsc_reduce", "nca_loss", "nca_rows", "kmeans_proxies",
            "have_ext"]

@@ -16,7 +16,7 @@ CSRC = os.path.join(REPO, "cilfw", "csrc")
 OUT = os.path.join(REPO, "cilfw", "_hip_lib.so")
 SOURCES = ["conv.hip", "norm.hip", "gemm.hip", "loss.hip", "util.hip",
            "data.hip", "nme.hip", "pod.hip", "cosine.hip", "mrank.hip",
-           "lsc.hip"]
+           "lsc.hip", "kmeans.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("CILFW_GPU_ARCH", "gfx950")
 
