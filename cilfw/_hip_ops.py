@@ -46,6 +46,8 @@ _PROTOS = {
     "cilfw_bn_bwd": [c_vp] * 11 + [c_vp, c_i] + [c_l, c_i, c_i, c_i, c_vp],
     "cilfw_add_relu_fwd": [c_vp] * 3 + [c_l, c_vp],
     "cilfw_add_relu_bwd": [c_vp] * 3 + [c_l, c_vp],
+    "cilfw_add_relu_tap_fwd": [c_vp] * 4 + [c_l, c_vp],
+    "cilfw_add_relu_tap_bwd": [c_vp] * 4 + [c_l, c_vp],
     "cilfw_downsample_a_fwd": [c_vp] * 2 + [c_i] * 4 + [c_vp],
     "cilfw_downsample_a_bwd": [c_vp] * 2 + [c_i] * 4 + [c_vp],
     "cilfw_gap_fwd": [c_vp] * 2 + [c_i] * 3 + [c_vp],
@@ -504,6 +506,55 @@ def add_relu_bwd(dy, y):
                             _stream())
     _check("add_relu_bwd")
     return da
+
+
+def _tap_buf(t, ref, name):
+    """bf16 buffer of ``ref``'s shape the tap kernels read or write with
+    16-byte vectors."""
+    _bf16(t, name)
+    assert t.shape == ref.shape and t.device == ref.device, \
+        f"{name}: {tuple(t.shape)} on {t.device} vs {tuple(ref.shape)} on " \
+        f"{ref.device}"
+    assert t.data_ptr() % 16 == 0, f"{name}: needs a 16-byte aligned tensor"
+    return t
+
+
+def add_relu_tap_fwd(a, b, out=None):
+    """-> (y, z): z = bf16(a + b), y = relu(z), bit-identical to
+    ``add_relu_fwd(a, b)``. ``out = (y, z)`` may be supplied (every element
+    of both is written)."""
+    _tap_buf(a, a, "add_relu_tap.a")
+    _tap_buf(b, a, "add_relu_tap.b")
+    y, z = out if out is not None else (torch.empty_like(a),
+                                        torch.empty_like(a))
+    _tap_buf(y, a, "add_relu_tap.y")
+    _tap_buf(z, a, "add_relu_tap.z")
+    assert y.data_ptr() != z.data_ptr() or a.numel() == 0
+    _lib.cilfw_add_relu_tap_fwd(_ptr(a), _ptr(b), _ptr(y), _ptr(z),
+                                c_l(a.numel()), _stream())
+    _check("add_relu_tap_fwd")
+    return y, z
+
+
+def add_relu_tap_bwd(dy, dz, z, out=None):
+    """g = bf16(dz + (z > 0 ? dy : 0)), the gradient of both inputs of
+    ``add_relu_tap_fwd``. ``dz=None`` is exactly ``add_relu_bwd(dy, y)``,
+    ``dy=None`` a copy of ``dz`` (one of the two must be given). ``out`` may
+    be supplied (every element is written)."""
+    assert dy is not None or dz is not None, \
+        "add_relu_tap_bwd: needs dy or dz"
+    _tap_buf(z, z, "add_relu_tap_bwd.z")
+    if dy is not None:
+        _tap_buf(dy, z, "add_relu_tap_bwd.dy")
+    if dz is not None:
+        _tap_buf(dz, z, "add_relu_tap_bwd.dz")
+    if out is None:
+        out = torch.empty_like(z)
+    _tap_buf(out, z, "add_relu_tap_bwd.out")
+    _lib.cilfw_add_relu_tap_bwd(_ptr(dy), _ptr(dz), _ptr(z), _ptr(out),
+                                c_l(z.numel()), _stream())
+    _check("add_relu_tap_bwd")
+    return out
 
 
 def downsample_a_fwd(x):

@@ -80,6 +80,14 @@ def get_args_parser():
                              "paper (0 = off: no map is requested, no POD "
                              "kernel runs; combine with --lambda_kd 0 for "
                              "POD without logit KD)")
+    parser.add_argument("--pod_tap", default="post", choices=["post", "pre"],
+                        help="maps POD-spatial pools: post = the stage "
+                             "outputs, after their last ReLU, which stays "
+                             "fused into the BN kernel; pre = the paper's "
+                             "tap before that ReLU: the last block of each "
+                             "stage then runs an unfused BN + one add+ReLU "
+                             "kernel that also writes the pre-activation, "
+                             "in every pass (needs --lambda_pod > 0)")
     parser.add_argument("--lambda_flat", default=0.0, type=float,
                         help="weight of the distillation of the final "
                              "embedding against the frozen teacher, 1 - cos "
@@ -249,6 +257,12 @@ def check_args(args):
         if not getattr(args, "mr_margin", 0.5) >= 0:
             raise ValueError(
                 f"--mr_margin must be >= 0 (got {args.mr_margin})")
+    if getattr(args, "pod_tap", "post") == "pre" \
+            and not getattr(args, "lambda_pod", 0.0) > 0:
+        raise ValueError(
+            "--pod_tap pre needs --lambda_pod > 0: without POD-spatial "
+            "nothing reads the pre-ReLU maps and the unfused block tails "
+            "only cost time")
     nb_proxy = getattr(args, "nb_proxy", 1)
     gamma = getattr(args, "proxy_gamma", 1.0)
     if not 1 <= nb_proxy <= 16:

@@ -390,6 +390,85 @@ void add_relu_bwd_kernel(const bf16_t* __restrict__ dy,
     da[i] = (bf2f(y[i]) > 0.f) ? dy[i] : (bf16_t)0;
 }
 
+// Tap variant of add+ReLU: the pre-activation z = bf16(a + b) is written
+// next to y = relu(z) (POD-spatial's pre-ReLU stage tap). RNE keeps the sign
+// and is monotone, so y is bit-identical to add_relu_fwd_kernel's.
+
+DEV bf16_t relu_bf(bf16_t z) { return bf2f(z) > 0.f ? z : (bf16_t)0; }
+
+__global__ __launch_bounds__(NT)
+void add_relu_tap_fwd_kernel(const bf16_t* __restrict__ a,
+                             const bf16_t* __restrict__ b,
+                             bf16_t* __restrict__ y, bf16_t* __restrict__ z,
+                             long total) {
+  long i0 = ((long)blockIdx.x * NT + threadIdx.x) * 8;
+  if (i0 >= total) return;
+  if (i0 + 8 <= total) {
+    int4 av = *(const int4*)&a[i0];
+    int4 bv = *(const int4*)&b[i0];
+    bf16_t* ae = (bf16_t*)&av;
+    bf16_t* be = (bf16_t*)&bv;
+    bf16_t oy[8], oz[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      oz[j] = f2bf(bf2f(ae[j]) + bf2f(be[j]));
+      oy[j] = relu_bf(oz[j]);
+    }
+    *(int4*)&z[i0] = *(int4*)oz;
+    *(int4*)&y[i0] = *(int4*)oy;
+  } else {
+    for (long i = i0; i < total; ++i) {
+      bf16_t s = f2bf(bf2f(a[i]) + bf2f(b[i]));
+      z[i] = s;
+      y[i] = relu_bf(s);
+    }
+  }
+}
+
+// g = bf16(dz + (z > 0 ? dy : 0)), the gradient of both a and b. Without dz
+// (HAS_DZ false) this is add_relu_bwd_kernel's bit copy of dy under the mask,
+// without dy a bit copy of dz; the launcher picks the instance, and an absent
+// operand is never read.
+
+template <bool HAS_DY, bool HAS_DZ>
+DEV bf16_t tap_grad(bf16_t dy, bf16_t dz, bf16_t z) {
+  if (!HAS_DY) return dz;
+  bool on = bf2f(z) > 0.f;
+  if (!HAS_DZ) return on ? dy : (bf16_t)0;
+  return f2bf(bf2f(dz) + (on ? bf2f(dy) : 0.f));
+}
+
+template <bool HAS_DY, bool HAS_DZ>
+__global__ __launch_bounds__(NT)
+void add_relu_tap_bwd_kernel(const bf16_t* __restrict__ dy,
+                             const bf16_t* __restrict__ dz,
+                             const bf16_t* __restrict__ z,
+                             bf16_t* __restrict__ g, long total) {
+  long i0 = ((long)blockIdx.x * NT + threadIdx.x) * 8;
+  if (i0 >= total) return;
+  if (i0 + 8 <= total) {
+    int4 yv = {0, 0, 0, 0}, dv = {0, 0, 0, 0}, zv = {0, 0, 0, 0};
+    if (HAS_DY) {
+      yv = *(const int4*)&dy[i0];
+      zv = *(const int4*)&z[i0];
+    }
+    if (HAS_DZ) dv = *(const int4*)&dz[i0];
+    bf16_t* ye = (bf16_t*)&yv;
+    bf16_t* de = (bf16_t*)&dv;
+    bf16_t* ze = (bf16_t*)&zv;
+    bf16_t og[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      og[j] = tap_grad<HAS_DY, HAS_DZ>(ye[j], de[j], ze[j]);
+    *(int4*)&g[i0] = *(int4*)og;
+  } else {
+    for (long i = i0; i < total; ++i)
+      g[i] = tap_grad<HAS_DY, HAS_DZ>(HAS_DY ? dy[i] : (bf16_t)0,
+                                      HAS_DZ ? dz[i] : (bf16_t)0,
+                                      HAS_DY ? z[i] : (bf16_t)0);
+  }
+}
+
 // ---------------------------------------------------------------- DownsampleA
 // y (N,ceil(H/2),ceil(W/2),2C): [:, :, :, :C] = x[:, ::2, ::2, :], rest zero
 // (AvgPool2d(1, 2) keeps the last row/column of an odd extent).
@@ -763,6 +842,28 @@ void cilfw_add_relu_bwd(const void* dy, const void* y, void* da, long total,
   hipLaunchKernelGGL(add_relu_bwd_kernel, dim3((int)blocks), dim3(NT), 0,
                      (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)y,
                      (bf16_t*)da, total);
+}
+
+void cilfw_add_relu_tap_fwd(const void* a, const void* b, void* y, void* z,
+                            long total, void* stream) {
+  if (total <= 0) return;
+  long blocks = (total + (long)NT * 8 - 1) / ((long)NT * 8);
+  hipLaunchKernelGGL(add_relu_tap_fwd_kernel, dim3((unsigned)blocks), dim3(NT),
+                     0, (hipStream_t)stream, (const bf16_t*)a,
+                     (const bf16_t*)b, (bf16_t*)y, (bf16_t*)z, total);
+}
+
+// dy or dz (not both) may be null: see add_relu_tap_bwd_kernel
+void cilfw_add_relu_tap_bwd(const void* dy, const void* dz, const void* z,
+                            void* g, long total, void* stream) {
+  if (total <= 0 || (dy == nullptr && dz == nullptr)) return;
+  long blocks = (total + (long)NT * 8 - 1) / ((long)NT * 8);
+  auto kern = dy == nullptr ? add_relu_tap_bwd_kernel<false, true>
+            : dz == nullptr ? add_relu_tap_bwd_kernel<true, false>
+                            : add_relu_tap_bwd_kernel<true, true>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), 0,
+                     (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)dz,
+                     (const bf16_t*)z, (bf16_t*)g, total);
 }
 
 void cilfw_downsample_a_fwd(const void* x, void* y, int N, int H, int W,

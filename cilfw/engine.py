@@ -515,7 +515,8 @@ def _run_tasks(args, device, watchdog):
                      head=getattr(args, "head", "linear"),
                      cos_scale_init=getattr(args, "cos_scale_init", 1.0),
                      nb_proxy=getattr(args, "nb_proxy", 1),
-                     proxy_gamma=getattr(args, "proxy_gamma", 1.0)
+                     proxy_gamma=getattr(args, "proxy_gamma", 1.0),
+                     pod_tap=getattr(args, "pod_tap", "post")
                      ).to(device)
     barrier()
 

@@ -159,8 +159,12 @@ HEAD_KINDS = ("linear", "cosine")
 
 class CilModel(nn.Module):
     def __init__(self, backbone_name, input_size=32, head="linear",
-                 cos_scale_init=1.0, nb_proxy=1, proxy_gamma=1.0):
+                 cos_scale_init=1.0, nb_proxy=1, proxy_gamma=1.0,
+                 pod_tap="post"):
         super().__init__()
+        if pod_tap not in resnet_cifar.POD_TAPS:
+            raise ValueError(f"unknown pod_tap {pod_tap!r} (one of "
+                             f"{resnet_cifar.POD_TAPS})")
         if head not in HEAD_KINDS:
             raise ValueError(f"unknown head kind {head!r} (one of "
                              f"{HEAD_KINDS})")
@@ -170,6 +174,9 @@ class CilModel(nn.Module):
         self.nb_proxy = int(nb_proxy)
         self.proxy_gamma = float(proxy_gamma)
         self.backbone = get_backbone(backbone_name, input_size)
+        # "pre": return_maps gives each stage's sum before its last ReLU (the
+        # paper's POD tap); a copy() of the model, the teacher, inherits it
+        self.backbone.pod_tap = pod_tap
         self.head_kind = head
         self.cos_scale_init = cos_scale_init
         self.fc = None
@@ -183,7 +190,8 @@ class CilModel(nn.Module):
 
     def forward(self, x, return_maps=False):
         """-> (logits, features); with ``return_maps`` -> (logits, features,
-        maps), maps = the backbone's stage outputs (for ops.pod_loss)."""
+        maps), maps = the backbone's stage maps (for ops.pod_loss): the stage
+        outputs, or with ``pod_tap="pre"`` their pre-ReLU sums."""
         if return_maps:
             features, maps = self.backbone(x, return_maps=True)
             return self.fc(features), features, maps

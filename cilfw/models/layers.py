@@ -50,7 +50,9 @@ class BatchNormAct2d(nn.Module):
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, tap=False):
+        """``tap`` (with a residual): the unfused tail, -> ``(y, z)`` with the
+        pre-activation ``z = bn(x) + residual`` next to ``y = relu(z)``."""
         # A frozen teacher's (mean, invstd) are precomputed once
         # (CilModel.cast_compute_weights_); that is only valid while the
         # running stats never change — a train-mode forward would update them
@@ -59,6 +61,15 @@ class BatchNormAct2d(nn.Module):
                     and getattr(self.running_mean, "_cilfw_frozen", None)
                     is not None), \
             "BN has precomputed frozen eval stats but is in train mode"
+        assert not tap or residual is not None, \
+            "tap=True needs the residual of a block tail"
+        if tap:
+            # the BN output feeds add_relu_tap, not a conv: fuse_bwd=False
+            out = CF.batchnorm_act(x, self.weight, self.bias,
+                                   self.running_mean, self.running_var,
+                                   self.momentum, self.eps, self.training,
+                                   relu=False, fuse_bwd=False)
+            return CF.add_relu_tap(out, residual)
         if residual is not None:
             # fused y = relu(bn(x) + residual) — residual-block tail
             return CF.batchnorm_add_relu(x, residual, self.weight, self.bias,

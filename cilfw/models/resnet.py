@@ -5,12 +5,18 @@ ResNet-18 on CIFAR-100 and ResNet-50 on ImageNet-1000, so these are cilfw-native
 additions. CIFAR inputs (<=64 px) get a 3x3/s1 stem with no max-pool; larger inputs
 get the classic 7x7/s2 stem + 3x3/s2 max-pool. Projection ("option B") shortcuts:
 1x1 conv + BN.
+
+``ResNet.pod_tap`` is ``CifarResNet.pod_tap``'s counterpart: ``"pre"`` makes the
+last block of each of the four stages take the unfused ``batchnorm_act`` +
+``add_relu_tap`` tail in every pass, and ``return_maps`` then returns the sums
+before each stage's last ReLU (the paper's POD tap) instead of the stage outputs.
 """
 
 import torch.nn as nn
 
 from ..ops import functional as CF
 from .layers import Conv2d, BatchNormAct2d
+from .resnet_cifar import POD_TAPS, run_stage_tapped
 
 
 class BasicBlockB(nn.Module):
@@ -28,9 +34,12 @@ class BasicBlockB(nn.Module):
         else:
             self.proj = None
 
-    def forward(self, x):
+    def forward(self, x, tap=False):
+        """``tap``: -> (y, z), the block output and its pre-ReLU sum."""
         out = self.bn1(self.conv1(x))
         residual = self.proj_bn(self.proj(x)) if self.proj is not None else x
+        if tap:
+            return self.bn2(self.conv2(out), residual, tap=True)
         return self.bn2(self.conv2(out), residual)  # fused bn+add+relu
 
 
@@ -52,10 +61,13 @@ class Bottleneck(nn.Module):
         else:
             self.proj = None
 
-    def forward(self, x):
+    def forward(self, x, tap=False):
+        """``tap``: -> (y, z), the block output and its pre-ReLU sum."""
         out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
         residual = self.proj_bn(self.proj(x)) if self.proj is not None else x
+        if tap:
+            return self.bn3(self.conv3(out), residual, tap=True)
         return self.bn3(self.conv3(out), residual)  # fused bn+add+relu
 
 
@@ -77,6 +89,7 @@ class ResNet(nn.Module):
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
         self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
         self.out_dim = 512 * block.expansion
+        self.pod_tap = "post"
 
     def _make_layer(self, block, width, n, stride):
         blocks = [block(self.in_ch, width, stride)]
@@ -86,10 +99,21 @@ class ResNet(nn.Module):
 
     def forward(self, x, return_maps=False):
         """-> (N, out_dim) features; with ``return_maps`` also the list of
-        the four stage outputs (NHWC, post-ReLU)."""
+        the four stage outputs (NHWC): post-ReLU, or with ``pod_tap == "pre"``
+        each stage's sum before its last ReLU."""
+        assert self.pod_tap in POD_TAPS, f"pod_tap {self.pod_tap!r}"
         x = self.stem_bn(self.stem(x))
         if not self.small_input:
             x = CF.max_pool(x, 3, 2, 1)
+        if self.pod_tap == "pre":
+            s1, z1 = run_stage_tapped(self.layer1, x)
+            s2, z2 = run_stage_tapped(self.layer2, s1)
+            s3, z3 = run_stage_tapped(self.layer3, s2)
+            s4, z4 = run_stage_tapped(self.layer4, s3)
+            feats = CF.global_avg_pool(s4)
+            if return_maps:
+                return feats, [z1, z2, z3, z4]
+            return feats
         s1 = self.layer1(x)
         s2 = self.layer2(s1)
         s3 = self.layer3(s2)

@@ -8,6 +8,13 @@ CilModel (reference template.py:87-123).
 
 cilfw differences (deliberate, MI355X-first): NHWC activations, fused BN+ReLU and
 add+ReLU epilogues, bf16 compute with fp32 master weights.
+
+``CifarResNet.pod_tap`` chooses the maps ``return_maps`` hands to POD-spatial:
+``"post"`` (default) the stage outputs, whose last ReLU is fused into
+``batchnorm_add_relu``; ``"pre"`` the paper's tap before that ReLU. Then the last
+block of each stage, in every pass, runs ``batchnorm_act`` + ``add_relu_tap``
+instead of the fused tail, so that the student, its evaluation and its frozen
+copy compute one function (the unfused tail rounds bn(x) to bf16 once more).
 """
 
 import torch
@@ -15,6 +22,18 @@ import torch.nn as nn
 
 from ..ops import functional as CF
 from .layers import Conv2d, BatchNormAct2d
+
+
+POD_TAPS = ("post", "pre")
+
+
+def run_stage_tapped(stage, x):
+    """Run a stage whose last block takes the tap path: -> (y, z), the stage
+    output the next stage consumes and its pre-ReLU sum (the POD map)."""
+    blocks = list(stage)
+    for blk in blocks[:-1]:
+        x = blk(x)
+    return blocks[-1](x, tap=True)
 
 
 class BasicBlockA(nn.Module):
@@ -31,9 +50,12 @@ class BasicBlockA(nn.Module):
             assert stride == 2 and out_ch == 2 * in_ch, \
                 "option-A downsample supports exactly stride2/double-channel"
 
-    def forward(self, x):
+    def forward(self, x, tap=False):
+        """``tap``: -> (y, z), the block output and its pre-ReLU sum."""
         out = self.bn_a(self.conv_a(x))
         residual = CF.downsample_a(x) if self.downsample else x
+        if tap:
+            return self.bn_b(self.conv_b(out), residual, tap=True)
         return self.bn_b(self.conv_b(out), residual)  # fused bn+add+relu
 
 
@@ -52,6 +74,7 @@ class CifarResNet(nn.Module):
         self.stage_2 = self._make_stage(16, 32, n, stride=2)
         self.stage_3 = self._make_stage(32, 64, n, stride=2)
         self.out_dim = 64
+        self.pod_tap = "post"
 
     @staticmethod
     def _make_stage(in_ch, out_ch, n, stride):
@@ -61,8 +84,18 @@ class CifarResNet(nn.Module):
 
     def forward(self, x, return_maps=False):
         """x: (N,H,W,C) NHWC -> (N, out_dim) features; with ``return_maps``
-        also the list of the three stage outputs (NHWC, post-ReLU)."""
+        also the list of the three stage outputs (NHWC): post-ReLU, or with
+        ``pod_tap == "pre"`` each stage's sum before its last ReLU."""
+        assert self.pod_tap in POD_TAPS, f"pod_tap {self.pod_tap!r}"
         x = self.bn_1(self.conv_1_3x3(x))
+        if self.pod_tap == "pre":
+            s1, z1 = run_stage_tapped(self.stage_1, x)
+            s2, z2 = run_stage_tapped(self.stage_2, s1)
+            s3, z3 = run_stage_tapped(self.stage_3, s2)
+            feats = CF.global_avg_pool(s3)
+            if return_maps:
+                return feats, [z1, z2, z3]
+            return feats
         s1 = self.stage_1(x)
         s2 = self.stage_2(s1)
         s3 = self.stage_3(s2)

@@ -1,5 +1,5 @@
 from .functional import (conv2d, batchnorm_act, batchnorm_add_relu, add_relu,
-                         downsample_a,
+                         add_relu_tap, downsample_a,
                          global_avg_pool, linear, cross_entropy, kd_loss, wa_loss,
                          accuracy, max_pool, crop_resize,
                          crop_resize_ragged, crop_resize_ragged_reference)
@@ -12,7 +12,7 @@ from .kmeans import kmeans_proxies
 from ._backend import have_ext
 
 __all__ = ["conv2d", "batchnorm_act", "batchnorm_add_relu", "add_relu",
-           "downsample_a",
+           "add_relu_tap", "downsample_a",
            "global_avg_pool", "linear", "cross_entropy", "kd_loss", "wa_loss", "accuracy",
            "max_pool", "crop_resize", "crop_resize_ragged",
            "crop_resize_ragged_reference", "nme_prototypes", "nme_topk",

@@ -471,6 +471,52 @@ def add_relu(a, b):
     return AddReLU.apply(a, b)
 
 
+class AddReLUTap(torch.autograd.Function):
+    """(y, z): z = a + b rounded to the dtype of ``a``, y = relu(z) — add+ReLU
+    that also hands out its pre-activation (POD-spatial's pre-ReLU stage tap).
+    Both outputs are differentiable; the gradient of either input is
+    ``dz + (z > 0 ? dy : 0)``, merged in one kernel. Only ``z`` is saved, and
+    a missing output gradient is not materialised (it reaches the kernel as a
+    null pointer)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.set_materialize_grads(False)
+        if use_hip(a):
+            y, z = ext().add_relu_tap_fwd(a, b)
+        else:
+            acc = torch.float64 if a.dtype == torch.float64 else torch.float32
+            z = (a.to(acc) + b.to(acc)).to(a.dtype)
+            y = torch.where(z > 0, z, torch.zeros_like(z))
+        ctx.save_for_backward(z)
+        return y, z
+
+    @staticmethod
+    def backward(ctx, dy, dz):
+        if dy is None and dz is None:
+            return None, None
+        (z,) = ctx.saved_tensors
+        dy = dy.contiguous() if dy is not None else None
+        dz = dz.contiguous() if dz is not None else None
+        if use_hip(z):
+            g = ext().add_relu_tap_bwd(dy, dz, z)
+        elif dy is None:
+            g = dz.clone()
+        else:
+            acc = torch.float64 if z.dtype == torch.float64 else torch.float32
+            g = dy.to(acc)
+            g = torch.where(z > 0, g, torch.zeros_like(g))
+            if dz is not None:
+                g = dz.to(acc) + g
+            g = g.to(z.dtype)
+        return g, g
+
+
+def add_relu_tap(a, b):
+    """-> (y, z) with z = a + b and y = relu(z); see AddReLUTap."""
+    return AddReLUTap.apply(a, b)
+
+
 # ------------------------------------------------------- downsample-A (reference C9)
 
 

@@ -17,8 +17,11 @@ Gradient of a stage loss with upstream scalar g — student only:
 ``da[n, h, w, c] = 2 a[n, h, w, c] (g_v.r[h, c] + g_v.q[w, c])`` in the dtype
 of ``a``.
 
-The paper taps each stage before its last ReLU; here that ReLU is fused into
-``batchnorm_add_relu``, so the post-ReLU stage outputs are used.
+The maps are whatever the backbones' ``return_maps`` gives: by default the
+post-ReLU stage outputs (their last ReLU is fused into
+``batchnorm_add_relu``); with ``pod_tap="pre"`` (``--pod_tap pre``) the paper's
+tap, each stage's sum before its last ReLU (``ops.add_relu_tap``). Nothing
+here assumes a sign: the pooled terms are squares.
 
 On a GPU the maps must be bf16 and the fused HIP kernels are the only path
 (no ATen fallback); CPU tensors use the torch implementation of the same

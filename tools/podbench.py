@@ -12,11 +12,21 @@ the shape, over that time, as a fraction of the 6.29 TB/s copy rate.
 (c) --engine: imgs/s of task 1 of a --gpu_data synthetic resnet18 run with
 --lambda_pod 0 and --lambda_pod 3, alternating, as the engine prints them
 (epoch 0 of the task holds the graph capture and is left out).
+(d) --tap-kernels: add_relu_tap_fwd / _bwd (the pre-ReLU tap of --pod_tap
+pre) next to add_relu_fwd / _bwd on the maps the tap really runs on: the
+CIFAR-ResNet stages and the resnet18 small-input stages at batch 128. The
+four alternate in one process; per kernel the median, the least and the most
+of ROUNDS timings of REPS back-to-back launches, the bytes it has to move and
+the time ratio tap / plain next to the byte ratio (4/3 both ways).
+(e) --engine --pod_tap pre: as (c), but --lambda_pod 3 in both runs and
+--pod_tap post against --pod_tap pre, alternating.
 
 Prints one JSON line per measurement.
 
-    python tools/podbench.py            # (a) and (b)
-    python tools/podbench.py --engine   # (c)
+    python tools/podbench.py                          # (a) and (b)
+    python tools/podbench.py --engine                 # (c)
+    python tools/podbench.py --tap-kernels            # (d)
+    python tools/podbench.py --engine --pod_tap pre   # (e)
 """
 import contextlib
 import io
@@ -134,7 +144,56 @@ def bench_shape(name, shape):
         kernels=kres, reps=REPS, rounds=ROUNDS)), flush=True)
 
 
-def engine_ips(lambda_pod, epochs=4):
+TAP_SHAPES = [("cifar/b128 s1", (128, 32, 32, 16)),
+              ("cifar/b128 s2", (128, 16, 16, 32)),
+              ("cifar/b128 s3", (128, 8, 8, 64)),
+              ("rn18/32px/b128 s1", (128, 32, 32, 64)),
+              ("rn18/32px/b128 s2", (128, 16, 16, 128)),
+              ("rn18/32px/b128 s3", (128, 8, 8, 256)),
+              ("rn18/32px/b128 s4", (128, 4, 4, 512))]
+
+
+def bench_tap(name, shape):
+    from cilfw import _hip_ops as H
+    g = torch.Generator(device=dev).manual_seed(2)
+    a, b, dy, dz = (torch.randn(shape, device=dev, generator=g
+                                ).to(torch.bfloat16) for _ in range(4))
+    y, z = H.add_relu_tap_fwd(a, b)
+    assert torch.equal(y, H.add_relu_fwd(a, b))
+    assert torch.equal(H.add_relu_tap_bwd(dy, None, z),
+                       H.add_relu_bwd(dy, y))
+    out2, out1 = (torch.empty_like(a), torch.empty_like(a)), \
+        torch.empty_like(a)
+    map_b = a.numel() * 2
+    kern = {"add_relu_fwd": (lambda: H.add_relu_fwd(a, b), 3 * map_b),
+            "add_relu_tap_fwd": (lambda: H.add_relu_tap_fwd(a, b, out=out2),
+                                 4 * map_b),
+            "add_relu_bwd": (lambda: H.add_relu_bwd(dy, y), 3 * map_b),
+            "add_relu_tap_bwd": (lambda: H.add_relu_tap_bwd(dy, dz, z,
+                                                            out=out1),
+                                 4 * map_b)}
+    for fn, _ in kern.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in kern}
+    for _ in range(ROUNDS):  # alternate the four
+        for k, (fn, _) in kern.items():
+            ts[k].append(ev_time(fn, REPS))
+    res = {k: dict(us_median=median(t) * 1e3, us_min=min(t) * 1e3,
+                   us_max=max(t) * 1e3, bytes=kern[k][1],
+                   frac_of_copy_rate=kern[k][1] / (median(t) * 1e-3)
+                   / COPY_RATE) for k, t in ts.items()}
+    print(json.dumps(dict(
+        shape=name, nhwc=shape, kernels=res, byte_ratio=4 / 3,
+        fwd_time_ratio=median(ts["add_relu_tap_fwd"])
+        / median(ts["add_relu_fwd"]),
+        bwd_time_ratio=median(ts["add_relu_tap_bwd"])
+        / median(ts["add_relu_bwd"]),
+        reps=REPS, rounds=ROUNDS)), flush=True)
+
+
+def engine_ips(lambda_pod, epochs=4, pod_tap=None):
     """imgs/s of the task-1 epochs after the first, as the engine prints."""
     from cilfw.config import parse_args
     from cilfw.engine import run
@@ -147,6 +206,8 @@ def engine_ips(lambda_pod, epochs=4):
             "--gpu_data", "--max_tasks", "2"]
     if lambda_pod:
         argv += ["--lambda_pod", str(lambda_pod)]
+    if pod_tap is not None:
+        argv += ["--pod_tap", pod_tap]
     out = io.StringIO()
     with contextlib.redirect_stdout(out):
         run(parse_args(argv))
@@ -154,15 +215,26 @@ def engine_ips(lambda_pod, epochs=4):
     assert "capture failed" not in out, out
     ips = [float(v) for v in re.findall(
         r"^task 1 epoch [1-9]\d*: .*imgs/s (\d+)$", out, re.M)]
-    return dict(lambda_pod=lambda_pod, task1_imgs_per_s=ips,
+    return dict(lambda_pod=lambda_pod, pod_tap=pod_tap or "post",
+                task1_imgs_per_s=ips,
                 pod_meter=bool(re.search(r"^task 1 .*  pod: ", out, re.M)))
 
 
 if __name__ == "__main__":
     assert torch.cuda.is_available(), "podbench needs a GPU"
-    if "--engine" in sys.argv:
+    if "--pod_tap" in sys.argv:
+        tap = sys.argv[sys.argv.index("--pod_tap") + 1]
+        assert tap in ("post", "pre") and "--engine" in sys.argv, \
+            "--pod_tap post|pre goes with --engine"
+        other = "post" if tap == "pre" else "pre"
+        for t in (other, tap, other, tap):
+            print(json.dumps(engine_ips(3, pod_tap=t)), flush=True)
+    elif "--engine" in sys.argv:
         for lam in (0, 3, 0, 3):
             print(json.dumps(engine_ips(lam)), flush=True)
+    elif "--tap-kernels" in sys.argv:
+        for name, shape in TAP_SHAPES:
+            bench_tap(name, shape)
     else:
         for name, shape in SHAPES:
             bench_shape(name, shape)
